@@ -9,12 +9,19 @@ score all K groups, sample, add), in frozen sub-sweeps of --batch rows, with
 the statistics update, group-set normalisation and cache rebuild included.
 Rows are generated on the device (seeded) before the timed region.
 
+A plain run sets up, warms up, times --steps steps and prints the line;
+--dump-outputs DIR also writes what the last timed step left (see
+dump_outputs).  Everything else the benchmark measures -- `step_breakdown`,
+`batch_variants`, `sustained`, `other_configs`, `exact_chains`,
+`strong_scaling` and `cpu_baseline`, each a run of its own after the timed
+region -- runs with --full only; without it those fields are null or empty.
+
 `--gpus N` with N > 1 starts N ranks itself (one process per GPU, backend
 nccl == RCCL) unless a launcher (torch.distributed.run) already set
 WORLD_SIZE; the parent never touches a GPU.  Rows are sharded, weak scaling
 (N rows per GPU), one all-reduce of the integer statistic deltas per
-sub-sweep; `strong_scaling` adds the same job with --rows split over the
-ranks.
+sub-sweep; `strong_scaling` (--full) adds the same job with --rows split over
+the ranks.
 
 Prints ONE JSON line (rank 0).  `roofline` prices the score+sample kernel
 (k_vs_sample, or k_sweep_sample / k_sweep_program where the value-sorted kernel
@@ -22,9 +29,10 @@ does not apply): its HIP-event duration on the launch stream is measured in
 this run; the counters behind `frac` (VALU busy cycles for the VALU-bound
 kernels, HBM bytes for the HBM-bound one) come from the rocprofv3 --pmc passes
 of this same command committed under profiles/ (profiles/r3_counters.json,
-ignored when the kernel sources changed since).  `cpu_baseline` times the
-oracle's sequential chain (the reference loop restated, oracle/oracle.c) on the
-first --cpu-rows rows of the very column the GPU holds, one host thread.
+ignored when the kernel sources changed since).  `cpu_baseline` (--full) times
+the oracle's sequential chain (the reference loop restated, oracle/oracle.c)
+on the first --cpu-rows rows of the very column the GPU holds, one host
+thread.
 """
 import argparse
 import hashlib
@@ -65,8 +73,17 @@ def parse():
     ap.add_argument("--alpha", type=float, default=1.0)
     ap.add_argument("--d", type=float, default=0.2)
     ap.add_argument("--seed", type=int, default=20240601)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs below that "
+                         "take runs of their own (CPU baseline, other "
+                         "sub-sweep sizes and configurations, sustained "
+                         "rate, exact chains, step breakdown, strong "
+                         "scaling); a plain run times --steps and stops")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to "
+                         "DIR/<name>.npy (float32/float64, 64 MB at most)")
     ap.add_argument("--cpu-rows", type=int, default=1_000_000,
-                    help="rows of the CPU-baseline sample (0 = skip)")
+                    help="rows of the CPU-baseline sample (--full; 0 = skip)")
     ap.add_argument("--config", default="dd",
                     choices=["dd", "dd16", "gp_nich", "dpd", "bb", "gp",
                              "nich", "mixed"],
@@ -99,22 +116,24 @@ def parse():
                          "their average; two events cost a sub-sweep 8 us): "
                          "1 all, 0 none")
     ap.add_argument("--other-batches", default="65536",
-                    help="comma-separated sub-sweep sizes timed besides "
-                         "--batch (a few steps each, reported in "
+                    help="--full: comma-separated sub-sweep sizes timed "
+                         "besides --batch (a few steps each, reported in "
                          "`batch_variants`; empty = none)")
     ap.add_argument("--other-configs", default="gp_nich,mixed,dpd",
-                    help="N = 1: the other BASELINE configurations timed "
-                         "besides the headline one (a few steps each, exact "
-                         "and scan sampling, reported in `other_configs` and "
-                         "as scalars in `config`; dpd = BASELINE configs[4] "
-                         "at K = 8192, V = 10 000; empty = none)")
+                    help="--full, N = 1: the other BASELINE configurations "
+                         "timed besides the headline one (a few steps each, "
+                         "exact and scan sampling, reported in "
+                         "`other_configs` and as scalars in `config`; dpd = "
+                         "BASELINE configs[4] at K = 8192, V = 10 000; "
+                         "empty = none)")
     ap.add_argument("--opt", action="append", default=[],
                     metavar="NAME=VALUE",
                     help="any other engine option (dist_gibbs_set_option), "
                          "e.g. rows_scratch=0; repeatable")
     ap.add_argument("--no-breakdown", action="store_true",
-                    help="skip the diagnostic pass behind `step_breakdown` "
-                         "(two sweeps with events at the phase boundaries)")
+                    help="--full: skip the diagnostic pass behind "
+                         "`step_breakdown` (two sweeps with events at the "
+                         "phase boundaries)")
     ap.add_argument("--torch-collectives", action="store_true",
                     help="keep the per-batch all-reduce on torch.distributed "
                          "instead of the library's own RCCL communicator")
@@ -122,7 +141,7 @@ def parse():
                     help="diagnostic: run the N>1 code path (statistic "
                          "deltas + RCCL all-reduce) with a single rank")
     ap.add_argument("--no-strong", action="store_true",
-                    help="N > 1: skip the strong-scaling leg")
+                    help="--full, N > 1: skip the strong-scaling leg")
     ap.add_argument("--placement", default="auto",
                     choices=["auto", "block", "value"],
                     help="N > 1: how rows are placed on the ranks.  value = "
@@ -133,12 +152,13 @@ def parse():
                          "anywhere, 3 + dim words per group; auto = value "
                          "where the feature list allows it")
     ap.add_argument("--sustained-seconds", type=float, default=2.0,
-                    help="N = 1: after the timed region the same job runs on "
-                         "for at least this long (`sustained_value`: the "
+                    help="--full, N = 1: after the timed region the same "
+                         "job runs on for at least this long "
+                         "(`sustained_value`: the "
                          "group count keeps creeping up; 0 = skip)")
     ap.add_argument("--exact-chains", type=int, default=1024,
-                    help="N = 1: independent exact chains (the reference's "
-                         "own sampler) run concurrently for "
+                    help="--full, N = 1: independent exact chains (the "
+                         "reference's own sampler) run concurrently for "
                          "`exact_chains_value`; 0 = skip")
     ap.add_argument("--exact-rows", type=int, default=20000,
                     help="rows each exact chain walks in its timed call "
@@ -247,6 +267,38 @@ def committed_counters(kernel):
     k = dict(k)
     k["stale"] = rec.get("source_hash") != source_hash()
     return k
+
+
+DUMP_BYTES = 64 << 20    # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, g, rank, world):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step -- every row's group id (`assignments.npy`, float32 while the ids are
+    below 2^24, exact) and every group's row count (`counts.npy`, float64).
+    The ranks of an N-rank run write their own rows (`*_rank<r>.npy`).  Rows
+    beyond the budget are sampled at a fixed stride, `assignments_rows.npy`
+    naming them."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world == 1 else "_rank%d" % rank
+    counts = g.counts().astype(np.float64)
+    assign = g.assignments()
+    dtype = np.float32
+    if assign.size and int(assign.max()) >= (1 << 24):
+        dtype = np.float64
+    size = np.dtype(dtype).itemsize
+    room = DUMP_BYTES // world - counts.nbytes - (1 << 16)   # (.npy headers)
+    files = {"counts": counts}
+    if assign.size * size > room:
+        # (a kept row costs its id and its float64 index)
+        keep = room // (size + 8)
+        rows = np.linspace(0, assign.size - 1, keep).astype(np.int64)
+        files["assignments_rows"] = rows.astype(np.float64)
+        assign = assign[rows]
+    files["assignments"] = assign.astype(dtype)
+    for name, arr in files.items():
+        np.save(os.path.join(path, name + tag + ".npy"), arr)
 
 
 def host_cpu():
@@ -622,7 +674,7 @@ def run_rank(args):
             return 2
         sharded.partition_by_value()
     column_host = None
-    if (rank == 0 and world == 1 and args.cpu_rows > 0
+    if (args.full and rank == 0 and world == 1 and args.cpu_rows > 0
             and args.config in ("dd", "dd16")):
         column_host = columns[0][:min(args.cpu_rows, n)].cpu().numpy()
 
@@ -643,13 +695,15 @@ def run_rank(args):
     draws = args.warmup + args.steps
     groups_at_end = len(g)
     comm_ms, comm_count = (g.core.comm_stats() if native_comm else (0.0, 0))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, g, rank, world)
 
     # where a sub-sweep's time goes: two more sweeps with events at the phase
     # boundaries (a diagnostic pass of its own: the events cost some 20 us a
     # sub-sweep, so the line's `value` is not measured with them)
     breakdown = None
-    if (rank == 0 and world == 1 and vs_batches and not args.force_collective
-            and not args.no_breakdown):
+    if (args.full and rank == 0 and world == 1 and vs_batches
+            and not args.force_collective and not args.no_breakdown):
         g.set_option("phase_timing", 1)
         g.core.phase_stats(reset=True)
         timed(sharded, g, n, args.batch, 2, 0, draws)
@@ -669,7 +723,9 @@ def run_rank(args):
     # the same job at other sub-sweep sizes (value depends on it: the
     # per-batch kernels and launch gaps do not shrink with the batch)
     variants = []
-    for b in [int(x) for x in args.other_batches.split(",") if x.strip()]:
+    other_batches = ([int(x) for x in args.other_batches.split(",")
+                      if x.strip()] if args.full else [])
+    for b in other_batches:
         if b == args.batch or b <= 0:
             continue
         steps_b = max(1, min(args.steps, 5))
@@ -711,7 +767,7 @@ def run_rank(args):
     # of device time; this is the rate over seconds of them, with the group
     # count the chain has reached by then (every kernel's work follows it)
     sustained = None
-    if (world == 1 and not args.force_collective
+    if (args.full and world == 1 and not args.force_collective
             and args.sustained_seconds > 0 and dt > 0):
         # (in stretches of what the timed region's rate predicts, until the
         # clock says so: the estimate is off both ways -- a long run pulls
@@ -733,7 +789,7 @@ def run_rank(args):
     # the general-row configurations (any feature list the value-sorted
     # kernels do not take), exact and with scan sampling
     others = []
-    if world == 1 and not args.force_collective:
+    if args.full and world == 1 and not args.force_collective:
         for cfg in [c.strip() for c in args.other_configs.split(",")
                     if c.strip()]:
             if cfg == args.config:
@@ -792,7 +848,7 @@ def run_rank(args):
     # one launch (BASELINE configs[3]: "independent chains"), same model and
     # group count as the headline
     exact = None
-    if (not args.force_collective and args.exact_chains > 0
+    if (args.full and not args.force_collective and args.exact_chains > 0
             and args.config in ("dd", "dd16")):
         # (N > 1: every rank runs its own chains -- "independent chains
         # sharded 1/GPU", no exchange at all: replicas only -- and the line
@@ -869,7 +925,7 @@ def run_rank(args):
         torch.cuda.empty_cache()
 
     strong = None
-    if world > 1 and not args.no_strong:
+    if args.full and world > 1 and not args.no_strong:
         # strong scaling: the SAME N rows in total, split over the ranks
         comm = sharded.native_comm
         del sharded, g, columns
@@ -1148,6 +1204,9 @@ def main():
     args = parse()
     if args.gpus < 1:
         sys.stderr.write("bench.py: --gpus must be >= 1\n")
+        return 2
+    if args.steps < 1 or args.warmup < 0:
+        sys.stderr.write("bench.py: --steps must be >= 1, --warmup >= 0\n")
         return 2
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args)

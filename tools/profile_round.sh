@@ -69,7 +69,7 @@ rm -rf $out/p_* $out/p.log
 cp $out/counters.json profiles/${tag}_counters.json
 # the bench line of record (the driver's command, with the CPU baseline), the
 # other configurations
-python3 bench.py --gpus 1 --steps 20 --warmup 5 2> $out/bench.log | tail -1 > $out/bench.json
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full 2> $out/bench.log | tail -1 > $out/bench.json
 : > $out/bench_other_configs.jsonl
 for c in nich gp bb dd16; do
   python3 $B --steps 3 --warmup 1 --config $c 2>/dev/null | tail -1 >> $out/bench_other_configs.jsonl
