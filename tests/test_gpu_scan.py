@@ -1,7 +1,7 @@
 """Scan sampling (option "sampling" = 1): the tolerance-level, opt-in mode of
 the batched row update -- one score evaluation per (row, group), a running
-log-sum-exp, the draw located by cumulative sums.  Same scores (bit for bit)
-and the same draw per row as the exact mode; the sampled index follows the
+log-sum-exp, the draw located by cumulative sums.  The same draw per row as
+the exact mode; the sampled index follows the
 same distribution (random.hpp:316-333, random.cc:94-106) but is computed with
 a different float summation order, so it may differ from the exact mode's
 where u * total falls within rounding of a boundary between two groups.
@@ -11,7 +11,11 @@ where u * total falls within rounding of a boundary between two groups.
       tests/util.py:182-203: goodness of fit > 1e-3);
 (ii)  agreement with the exact mode on the same batch (> 99.5 % asserted;
       the measured rate is printed);
-(iii) the scores are the exact mode's, bit for bit."""
+(iii) row_scores() of the two engines are equal bit for bit.  That call runs
+      its own launch whatever `sampling` is set to, so it checks the shared
+      scoring, not the scores the scan kernels compute internally; those are
+      held row by row to the float64 inverse CDF in
+      tests/test_gpu_sampler_f64.py."""
 import numpy as np
 import pytest
 from scipy import stats
@@ -52,6 +56,7 @@ def test_scan_agrees_with_exact_on_one_batch(config, k):
         out.append((gpu.assignments().copy(), scores))
         assert gpu.core.debug_counts()["scratch_batches"] == 1
     (exact, s0), (scan, s1) = out
+    # (row_scores' own launch on both engines, not the scan kernel's scores)
     assert np.array_equal(s0.view(np.uint32), s1.view(np.uint32))
     agree = float((exact == scan).mean())
     first = np.nonzero(exact != scan)[0]
