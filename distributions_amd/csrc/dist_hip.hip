@@ -1091,7 +1091,7 @@ struct Gibbs {
     std::vector<std::unique_ptr<VsCache>> vs_cache;
     std::vector<std::pair<size_t, size_t>> vs_ranges;   // [r0, r1) of each
     size_t vs_last = 0;   // where the last look-up found its range
-    DeviceBuf<float> vsLA, vsLB, vsM, vsmB, vsPA, vsPB, vsOwn;
+    DeviceBuf<float> vsLA, vsLB, vsM, vsmB, vsPA, vsPB, vsOwn, vsTot;
     DeviceBuf<int> remap_log;   // the batches' swap-removals (kernels.h)
     // the removal epoch (DevState::pad) the groups' recorded offsets are
     // stamped with (VsOffsets): carried from one device-normalised run to the
@@ -1229,6 +1229,10 @@ struct Gibbs {
                || c.n_tiles < (Kpad <= 1152 ? kVsNarrowBelowTiles : 4100u);
     }
     int running_sums_min_tiles = 2048;   // see sample_value_sorted
+    // k_vs_tables builds every (value, group) cell's sampling total
+    // (VsTables::tot): 0 never, 1 where the running sums would be built
+    // (default), 2 whenever k_vs_tables runs
+    int shared_totals_mode = 1;
     int cu_count_cached = 0;
     int cu_count() {
         if (!cu_count_cached) {
@@ -2807,6 +2811,11 @@ struct Gibbs {
         const bool large = !narrow
                            && c.n_tiles >= (uint32_t)running_sums_min_tiles;
         const bool prefix = large && Kpad <= 8192;
+        // ... or, where k_vs_tables runs, the cells' totals in their place:
+        // its idle threads fold them while the tiles skip their total pass
+        const bool totals =
+            fused && (shared_totals_mode == 2
+                      || (shared_totals_mode == 1 && prefix));
         // the arg-max group's rows get a tile of their own per value when the
         // launch is large (and group-sorted: k_vs_apply's LDS sort fits)
         // ... and their workgroups do not push the launch past what is
@@ -2832,11 +2841,12 @@ struct Gibbs {
         last_prefix = prefix;
         band_batches += bands ? 1 : 0;
         prefix_batches += prefix ? 1 : 0;
-        if (prefix) {
+        if (prefix && !totals) {
             vsPA.reserve(grow_capacity((size_t)nv * (Kpad / kVsUnroll)), 0);
             vsPB.reserve(grow_capacity((size_t)nv * (Kpad / kVsUnroll)), 0);
         }
         if (fused) vsOwn.reserve(grow_capacity((size_t)nv * Kpad), 0);
+        if (totals) vsTot.reserve(grow_capacity((size_t)nv * Kpad), 0);
         deferred.reserve(std::max<size_t>(n, 1), 0);
         deferred_count.reserve(1, 0);
         // base[], base_single[] and the scalars; the few handed-over rows
@@ -2853,13 +2863,14 @@ struct Gibbs {
         P.assign_pos = c.assign_pos.p;
         VsLaunch L{this, &P, &c,
                    VsTables{vsLA.p, vsLB.p, vsM.p, vsmB.p, vsArg.p, Kpad,
-                            prefix ? vsPA.p : nullptr,
-                            prefix ? vsPB.p : nullptr,
+                            prefix && !totals ? vsPA.p : nullptr,
+                            prefix && !totals ? vsPB.p : nullptr,
                             bands ? vsBandMode.p : nullptr,
                             bands ? vsBandTile.p : nullptr, c.val_start.p,
                             nv, nullptr, c.chunk_first.p,
                             fused ? vsOwn.p : nullptr, Kuse, band_count,
-                            fused ? 1 : 0, sample_prio_mode}, narrow, fused};
+                            fused ? 1 : 0, sample_prio_mode,
+                            totals ? vsTot.p : nullptr}, narrow, fused};
         // DIST_VS_STAMPS=<file>: per-wave phase stamps of every launch (the
         // last one stays in the file): tools/vs_stamps.py
         static const char * stamps_path = getenv("DIST_VS_STAMPS");
@@ -6028,7 +6039,8 @@ int dist_gibbs_set_option(dist_gibbs_t * g, const char * name, int value) {
             "sequential_chain", "running_sums_min_tiles", "narrow_read_ahead",
             "stream_scratch", "rows_scratch", "rows_scratch_lds_log",
             "rows_scratch_block", "rows_fold", "apply_stage", "program_all",
-            "sample_prio", "rows_prio", "apply_overlap", "run_batches_cap"};
+            "sample_prio", "rows_prio", "apply_overlap", "run_batches_cap",
+            "shared_totals"};
         bool is_hook = false;
         for (const char * h : hooks) is_hook = is_hook || key == h;
         DIST_REQUIRE(hook == is_hook,
@@ -6099,6 +6111,12 @@ int dist_gibbs_set_option(dist_gibbs_t * g, const char * name, int value) {
             // do not depend on it)
             DIST_REQUIRE(value >= 0, "running_sums_min_tiles: >= 0");
             g->impl->running_sums_min_tiles = value;
+        } else if (key == "shared_totals") {
+            // k_vs_tables folds every (value, group) cell's sampling total
+            // and the tiles skip their total pass: 0 never, 1 where the
+            // library chooses (default), 2 whenever k_vs_tables runs
+            DIST_REQUIRE(value >= 0 && value <= 2, "shared_totals: 0, 1 or 2");
+            g->impl->shared_totals_mode = value;
         } else if (key == "rows_scratch") {
             // general rows: 3 k_rows_scratch (default), 0 k_sweep_program
             // (what feature lists beyond k_rows_scratch's table take anyway)

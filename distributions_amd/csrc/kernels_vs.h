@@ -114,6 +114,14 @@ struct VsTables {
     // wave priorities by phase (0: none; 0x10000 | set-up << 12 | total <<
     // 8 | the scan's first half << 4 | its second half): see k_vs_sample
     int prio_mode;
+    // [nvals][Kpad] (k_vs_tables; null = not built) the sampling total of a
+    // row of value x in group k, own slot replaced by own[x][k]:
+    //   ((e_0 + e_1) + e_2) + ... + e_{Kw-1},  e_j = L[x][j] (j != k), own[x][k]
+    // with L = LB for the arg-max group, LA for the others -- the float the
+    // tiles' total pass computes per row.  Entries whose own[] is -1 or
+    // k >= the group count are not read.  With it the tiles run the scan only
+    // (and PA / PB are not built).
+    float * tot;
 };
 constexpr uint32_t kVsBandWalkRows = 8192;
 
@@ -398,6 +406,116 @@ struct TablesParams {
 constexpr int kTablesBlock = 1024;
 constexpr int kTablesPer = 8;            // groups per thread
 constexpr int kTablesMaxK = kTablesBlock * kTablesPer;
+
+typedef float v2f __attribute__((ext_vector_type(2)));
+// acc + {w.y, w.y}: v_pk_add_f32 reads the pair's high half into both lanes
+// itself (op_sel), where the compiler would copy it into a register first
+__device__ __forceinline__ v2f vs_pk_add_hi(v2f acc, v2f w) {
+    v2f r;
+    asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]"
+        : "=v"(r) : "v"(w), "v"(acc));
+    return r;
+}
+// k_vs_tables' sampling totals (VsTables::tot): every (value, group) cell's
+// in-order fold of its likelihood vector, own slot replaced, is the same float
+// for every row of the cell, so the tables compute it once instead of each
+// tile's rows recomputing it.  A job is a window of kTotWindow consecutive
+// groups, two neighbours per lane (one v_pk_add_f32 per entry, from 0.0f,
+// strictly in index order), or -- one job more -- the arg-max group's fold
+// of LB.  The entries come from the copies in LDS (uniform addresses:
+// broadcast), read a chunk ahead.  Inside the window the entry pair (j, j+1)
+// is the own pair of ONE lane, (j - window) / 2: one compare and two selects
+// per pair.
+constexpr int kTotWindow = 128;   // groups per job: two per lane
+__device__ __forceinline__ void vs_tot_chunk(v2f & acc, const float4 (&w)[8],
+                                             int own_lane, float o0,
+                                             float o1) {
+    // own_lane: this lane's pair index inside the chunk (0..15: in it)
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const v2f lo = {w[q].x, w[q].y}, hi = {w[q].z, w[q].w};
+        const bool s0 = own_lane == 2 * q, s1 = own_lane == 2 * q + 1;
+        acc += (v2f){s0 ? o0 : lo.x, lo.x};
+        acc += (v2f){lo.y, s0 ? o1 : lo.y};
+        acc += (v2f){s1 ? o0 : hi.x, hi.x};
+        acc += (v2f){hi.y, s1 ? o1 : hi.y};
+    }
+}
+__device__ __forceinline__ void vs_tot_plain(v2f & acc, const float4 (&w)[8]) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        acc += (v2f){w[q].x, w[q].x};
+        acc = vs_pk_add_hi(acc, (v2f){w[q].x, w[q].y});
+        acc += (v2f){w[q].z, w[q].z};
+        acc = vs_pk_add_hi(acc, (v2f){w[q].z, w[q].w});
+    }
+}
+__device__ __forceinline__ void vs_tables_totals(
+        float * tot, const float * lds_a, const float * lds_b,
+        const float * lds_o, int K1, int Kw, int amax, int wave, int lane) {
+    constexpr int Q = kVsUnroll / 4;
+    static_assert(Q == 8, "a chunk is eight float4");
+    if (K1 <= 0) return;
+    const int nwin = (K1 + kTotWindow - 1) / kTotWindow;
+    const int nchunks = Kw / kVsUnroll;   // >= 1
+    for (int job = wave; job <= nwin; job += kTablesBlock / 64) {
+        const bool arg = job == nwin;   // the arg-max group, over LB
+        const float4 * src =
+            reinterpret_cast<const float4 *>(arg ? lds_b : lds_a);
+        const int wlo = job * kTotWindow;
+        const int k0 = arg ? amax : wlo + 2 * lane;
+        float o0, o1;
+        if (arg) {
+            o0 = o1 = lds_o[amax];
+        } else {
+            float2 ov = {0.f, 0.f};
+            if (k0 < Kw) ov = *reinterpret_cast<const float2 *>(lds_o + k0);
+            o0 = ov.x;
+            o1 = ov.y;
+        }
+        // the chunks with own slots, and this lane's pair in each
+        const int c_lo = arg ? amax / kVsUnroll : wlo / kVsUnroll;
+        const int c_hi = arg ? c_lo + 1 : c_lo + kTotWindow / kVsUnroll;
+        const int pair = arg ? (amax % kVsUnroll) / 2 : lane;
+        v2f acc = {0.f, 0.f};
+        auto add_chunk = [&](const float4 (&w)[Q], int c) {
+            if (c >= c_lo && c < c_hi) {
+                // (the arg-max job: every lane's pair holds the group, in
+                // the half of its parity)
+                vs_tot_chunk(acc, w,
+                             arg ? pair : pair - (c - c_lo) * (kVsUnroll / 2),
+                             o0, o1);
+            } else {
+                vs_tot_plain(acc, w);
+            }
+        };
+        float4 even[Q], odd[Q];   // ping-pong: no register copies
+#pragma unroll
+        for (int q = 0; q < Q; ++q) even[q] = src[q];
+        for (int c = 0; c < nchunks; c += 2) {
+            const int c1 = c + 1 < nchunks ? c + 1 : c;
+#pragma unroll
+            for (int q = 0; q < Q; ++q) odd[q] = src[c1 * Q + q];
+            __builtin_amdgcn_sched_barrier(0);   // loads first
+            add_chunk(even, c);
+            __builtin_amdgcn_sched_barrier(0);
+            if (c + 1 >= nchunks) break;
+            const int c2 = c + 2 < nchunks ? c + 2 : c;
+#pragma unroll
+            for (int q = 0; q < Q; ++q) even[q] = src[c2 * Q + q];
+            __builtin_amdgcn_sched_barrier(0);
+            add_chunk(odd, c + 1);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (arg) {
+            if (lane == 0) tot[amax] = (amax & 1) ? acc.y : acc.x;
+        } else {
+            if (k0 < Kw && k0 != amax) tot[k0] = acc.x;
+            if (k0 + 1 < Kw && k0 + 1 != amax) tot[k0 + 1] = acc.y;
+        }
+    }
+}
+
 template <int KIND>
 __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
                                                             VsTables T) {
@@ -657,7 +775,11 @@ __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
     float * lb = T.LB + (size_t)x * Kpad;
     float * lds_a = tb_lds;
     float * lds_b = tb_lds + Kpad;
-    const bool chains = T.PA != nullptr;
+    // (the totals' own-slot likelihoods: where the plan's vanished-before
+    // counts were, read for the last time before the barrier behind src_of)
+    float * lds_o = reinterpret_cast<float *>(before);
+    const bool totals = T.tot != nullptr;
+    const bool chains = T.PA != nullptr || totals;
     // (the tiles read whole chunks of kVsUnroll entries up to the group count:
     // that far the vectors are written, zeros behind the last group)
     const int Kw = min(Kpad, (K1 + kVsUnroll - 1) / kVsUnroll * kVsUnroll);
@@ -684,6 +806,7 @@ __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
         lb[k] = b;
         if (T.own) T.own[(size_t)x * Kpad + k] = o;
         if (chains) { lds_a[k] = a; lds_b[k] = b; }
+        if (totals) lds_o[k] = o;
     }
     // ---- workgroup 0: the id maps (mixture.hpp:474-497), the scalars, the
     // new state
@@ -803,10 +926,15 @@ __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
             T.band_tile[c] = band;
         }
     }
-    // ---- the running sums at the chunk boundaries (see k_vs_prepare): two
-    // lanes walk the copies in LDS
     if (!chains) return;
     __syncthreads();
+    if (totals) {
+        vs_tables_totals(T.tot + (size_t)x * Kpad, lds_a, lds_b, lds_o, K1, Kw,
+                         amax, wave, lane);
+        return;
+    }
+    // ---- the running sums at the chunk boundaries (see k_vs_prepare): two
+    // lanes walk the copies in LDS
     if (wave < 2 && lane == 0) {
         const float4 * src =
             reinterpret_cast<const float4 *>(wave ? lds_b : lds_a);
@@ -876,7 +1004,6 @@ __device__ __forceinline__ void vs_set_prio(int p) {
     default: __builtin_amdgcn_s_setprio(3); break;
     }
 }
-typedef float v2f __attribute__((ext_vector_type(2)));
 static_assert(kVsR == 2, "the recurrences below are written for two rows per "
                          "lane (one v_pk_add_f32 per entry)");
 __device__ __forceinline__ v2f vs_splat(float x) { return (v2f){x, x}; }
@@ -902,7 +1029,8 @@ __device__ __forceinline__ void vs_sum_and_scan(
         uniform_fp lp, const float * lp_vec, uniform_fp prefix, int K,
         const int (&g)[kVsR],
         const float (&l_own)[kVsR], const float (&u)[kVsR],
-        const bool (&active)[kVsR], int (&found)[kVsR], int prio_steps
+        const bool (&active)[kVsR], int (&found)[kVsR], int prio_steps,
+        bool shared, const float (&shared_total)[kVsR]
 #ifdef DIST_VS_STAMPS
         , int & chunks_done
 #endif
@@ -915,49 +1043,55 @@ __device__ __forceinline__ void vs_sum_and_scan(
     }
     // a lane's two rows advance together: .x is tile row 2*lane, .y the next
     // one (neighbours in the group-sorted tile, so they share own-slot pieces)
-    // no own slot before the tile's first own chunk: start from the value's
-    // running sum at that boundary (k_vs_prepare)
-    int c_first = 0;
-    float start = 0.f;
-    if (prefix) {
-        const int nchunks = (K + kVsUnroll - 1) / kVsUnroll;
-        int m = min(active[0] ? gchunk[0] : nchunks,
-                    active[1] ? gchunk[1] : nchunks);
+    // `shared`: the totals are the (value, group) cells' (k_vs_tables,
+    // VsTables::tot), the same floats; the scan starts right away
+    v2f total = {shared_total[0], shared_total[1]};
+    if (!shared) {
+        // no own slot before the tile's first own chunk: start from the
+        // value's running sum at that boundary (k_vs_prepare)
+        int c_first = 0;
+        float start = 0.f;
+        if (prefix) {
+            const int nchunks = (K + kVsUnroll - 1) / kVsUnroll;
+            int m = min(active[0] ? gchunk[0] : nchunks,
+                        active[1] ? gchunk[1] : nchunks);
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) m = min(m, __shfl_xor(m, off));
-        c_first = __builtin_amdgcn_readfirstlane(m);
-        if (c_first >= nchunks) c_first = 0;   // (no active lane)
-        start = prefix[c_first];
-    }
-    v2f total = {start, start};
-    for (int c = c_first, k0 = c_first * kVsUnroll; k0 < K;
-         ++c, k0 += kVsUnroll) {
-        float l[kVsUnroll];
-        vs_fetch_chunk(lp, k0, l);
+            for (int off = 32; off > 0; off >>= 1)
+                m = min(m, __shfl_xor(m, off));
+            c_first = __builtin_amdgcn_readfirstlane(m);
+            if (c_first >= nchunks) c_first = 0;   // (no active lane)
+            start = prefix[c_first];
+        }
+        total = (v2f){start, start};
+        for (int c = c_first, k0 = c_first * kVsUnroll; k0 < K;
+             ++c, k0 += kVsUnroll) {
+            float l[kVsUnroll];
+            vs_fetch_chunk(lp, k0, l);
 #ifdef DIST_VS_STAMPS
-        ++chunks_done;
+            ++chunks_done;
 #endif
-        if (__any(gchunk[0] == c || gchunk[1] == c)) {
-            // own slots of a group-sorted tile are neighbours: only the
-            // eight-entry pieces that hold one take the per-lane select
+            if (__any(gchunk[0] == c || gchunk[1] == c)) {
+                // own slots of a group-sorted tile are neighbours: only the
+                // eight-entry pieces that hold one take the per-lane select
 #pragma unroll
-            for (int b = 0; b < kVsUnroll / 8; ++b) {
-                const int piece = (k0 >> 3) + b;
-                if (__any(gpiece[0] == piece || gpiece[1] == piece)) {
-                    const float l8[8] = {l[8 * b], l[8 * b + 1], l[8 * b + 2],
-                                         l[8 * b + 3], l[8 * b + 4],
-                                         l[8 * b + 5], l[8 * b + 6],
-                                         l[8 * b + 7]};
-                    vs_own_piece<false>(total, l8, k0 + 8 * b, g, l_own);
-                } else {
+                for (int b = 0; b < kVsUnroll / 8; ++b) {
+                    const int piece = (k0 >> 3) + b;
+                    if (__any(gpiece[0] == piece || gpiece[1] == piece)) {
+                        const float l8[8] = {l[8 * b], l[8 * b + 1],
+                                             l[8 * b + 2], l[8 * b + 3],
+                                             l[8 * b + 4], l[8 * b + 5],
+                                             l[8 * b + 6], l[8 * b + 7]};
+                        vs_own_piece<false>(total, l8, k0 + 8 * b, g, l_own);
+                    } else {
 #pragma unroll
-                    for (int j = 8 * b; j < 8 * b + 8; ++j)
-                        total += vs_splat(l[j]);
+                        for (int j = 8 * b; j < 8 * b + 8; ++j)
+                            total += vs_splat(l[j]);
+                    }
                 }
-            }
-        } else {
+            } else {
 #pragma unroll
-            for (int j = 0; j < kVsUnroll; ++j) total += vs_splat(l[j]);
+                for (int j = 0; j < kVsUnroll; ++j) total += vs_splat(l[j]);
+            }
         }
     }
     // t never increases, so the number of chunks that END with t > 0 is the
@@ -1064,7 +1198,9 @@ void k_vs_sample(
     // with a band tile everything else
 #ifdef DIST_VS_STAMPS   // diagnostic build only (make stamps): costs 3 us
     unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0;
-    int chunks_done = 0;   // chunks of both recurrences, both vectors
+    // chunks of both recurrences, both vectors (of the scan only where the
+    // totals are shared, T.tot)
+    int chunks_done = 0;
     if (T.stamps) st0 = __builtin_amdgcn_s_memtime();
 #endif
     // A SIMD issues from its oldest ready wave: at equal priority the waves
@@ -1076,6 +1212,8 @@ void k_vs_sample(
     // total, the total ahead of the scan and the scan's first half ahead of
     // its second, whoever is behind goes first and a SIMD's waves end
     // together: 69 -> 64 us per launch at C2 (profiles/r5_wave_priorities.txt).
+    // (With shared totals, T.tot, there is no total phase: its level holds
+    // for the moment between set-up and scan.)
     if (T.prio_mode) vs_set_prio(T.prio_mode >> 12);
     const bool band = id < n_band_ids;
     const VsTile * mine = band ? T.band_tile + id : tiles + (id - n_band_ids);
@@ -1101,8 +1239,9 @@ void k_vs_sample(
     bool valid[kVsR], inA[kVsR], inB[kVsR];
     size_t row[kVsR];
     int g[kVsR], g2[kVsR];
-    float l_own[kVsR], u[kVsR];
+    float l_own[kVsR], u[kVsR], total[kVsR];
     bool anyA = false, anyB = false;
+    const bool shared = T.tot != nullptr;   // (only with T.own)
 #pragma unroll
     for (int r = 0; r < kVsR; ++r) {
         valid[r] = (uint32_t)(kVsR * lane + r) < n;
@@ -1111,6 +1250,7 @@ void k_vs_sample(
         g2[r] = 0;
         l_own[r] = 0.f;
         u[r] = 0.f;
+        total[r] = 0.f;
         bool classB = false;
         if (valid[r]) {
             const uint32_t at = pos + kVsR * lane + r;
@@ -1124,6 +1264,7 @@ void k_vs_sample(
             bool defer;
             if (T.own) {   // (k_vs_tables did this per (value, group))
                 l_tab = T.own[(size_t)x * T.Kpad + g[r]];
+                if (shared) total[r] = T.tot[(size_t)x * T.Kpad + g[r]];
                 defer = l_tab < 0.f;
             } else {
                 const int n_g = P.counts[g[r]];
@@ -1175,7 +1316,8 @@ void k_vs_sample(
         vs_sum_and_scan(as_uniform(vec), vec,
                         T.PA ? as_uniform(T.PA + (size_t)x
                                           * (T.Kpad / kVsUnroll)) : nullptr,
-                        K, g, l_own, u, inA, f, both ? 0 : T.prio_mode
+                        K, g, l_own, u, inA, f, both ? 0 : T.prio_mode,
+                        shared, total
 #ifdef DIST_VS_STAMPS
                         , chunks_done
 #endif
@@ -1192,7 +1334,8 @@ void k_vs_sample(
         vs_sum_and_scan(as_uniform(vec), vec,
                         T.PB ? as_uniform(T.PB + (size_t)x
                                           * (T.Kpad / kVsUnroll)) : nullptr,
-                        K, g, l_own, u, inB, f, both ? 0 : T.prio_mode
+                        K, g, l_own, u, inB, f, both ? 0 : T.prio_mode,
+                        shared, total
 #ifdef DIST_VS_STAMPS
                         , chunks_done
 #endif
