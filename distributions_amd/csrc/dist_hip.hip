@@ -4564,16 +4564,29 @@ struct Gibbs {
         row_scores.download(out, (size_t)n);
         *size_out = (size_t)n;
     }
+    // k_score_rows takes one work-item per (row, group): a launch covers at
+    // most this many (debug.score_rows_chunk lowers it), whole rows each
+    size_t score_rows_chunk = (size_t)1 << 30;
     void score_rows(size_t r0, size_t r1, float * out_dev, size_t ld) {
         DIST_REQUIRE(r0 <= r1 && r1 <= n_rows && ld >= (size_t)K(),
                      "bad row range or leading dimension");
         DIST_REQUIRE(r1 <= assigned_rows || r0 == r1,
                      "rows without a group yet: init_sequential first");
+        // the caches it reads are the frozen state's only between batches
+        DIST_REQUIRE(!batch_open, "batch open");
         if (r0 == r1) return;
         flush_assign_pos();
         SweepParams P = params(r0, r1, 0, 0);
         prepare(P);
-        LAUNCH(k_score_rows, (r1 - r0) * (size_t)K(), P, out_dev, ld);
+        const size_t step =
+            std::max<size_t>(1, score_rows_chunk / (size_t)K());
+        for (size_t c0 = r0; c0 < r1; c0 += step) {
+            const size_t c1 = std::min(r1, c0 + step);
+            P.row_begin = c0;
+            P.row_end = c1;
+            LAUNCH(k_score_rows, (c1 - c0) * (size_t)K(), P,
+                   out_dev + (c0 - r0) * ld, ld);
+        }
     }
 };
 
@@ -6040,7 +6053,7 @@ int dist_gibbs_set_option(dist_gibbs_t * g, const char * name, int value) {
             "stream_scratch", "rows_scratch", "rows_scratch_lds_log",
             "rows_scratch_block", "rows_fold", "apply_stage", "program_all",
             "sample_prio", "rows_prio", "apply_overlap", "run_batches_cap",
-            "shared_totals"};
+            "shared_totals", "score_rows_chunk"};
         bool is_hook = false;
         for (const char * h : hooks) is_hook = is_hook || key == h;
         DIST_REQUIRE(hook == is_hook,
@@ -6111,6 +6124,11 @@ int dist_gibbs_set_option(dist_gibbs_t * g, const char * name, int value) {
             // do not depend on it)
             DIST_REQUIRE(value >= 0, "running_sums_min_tiles: >= 0");
             g->impl->running_sums_min_tiles = value;
+        } else if (key == "score_rows_chunk") {
+            // the most (row, group) work-items one k_score_rows launch
+            // takes (default 2^30, under the 2^32 of a 1-D grid)
+            DIST_REQUIRE(value > 0, "score_rows_chunk: > 0");
+            g->impl->score_rows_chunk = (size_t)value;
         } else if (key == "shared_totals") {
             // k_vs_tables folds every (value, group) cell's sampling total
             // and the tiles skip their total pass: 0 never, 1 where the

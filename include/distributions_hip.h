@@ -540,7 +540,9 @@ int dist_gibbs_comm_volume(dist_gibbs_t * g, uint64_t out[4], int reset);
 int dist_gibbs_row_scores(dist_gibbs_t * g, size_t row, float * scores_out,
                           size_t * size_out);
 /* score_values extension: scores[r * ld + k] for rows [row_begin,row_end)
- * against the current state (no self-removal), device output */
+ * against the current state (no self-removal), device output; columns K..ld-1
+ * are not written.  Refused while a batch is open (as dist_gibbs_row_scores);
+ * launched in chunks of whole rows under the 1-D grid limit. */
 int dist_gibbs_score_rows_dev(dist_gibbs_t * g, size_t row_begin,
                               size_t row_end, float * scores_dev, size_t ld);
 
@@ -676,7 +678,8 @@ int dist_gibbs_sharded_device_normalise_ok(const dist_gibbs_t * g,
  * chunk's few handed-over rows while its other waves add up the moves: 1 | 0
  * before they do), run_batches_cap (a device-normalised run covers at most
  * this many batches: 0 as many as fit -- tests/test_gpu_native_ranks.py sees a
- * run used up and the ranks agree on the next one).
+ * run used up and the ranks agree on the next one), score_rows_chunk (the most
+ * (row, group) work-items one dist_gibbs_score_rows_dev launch takes: 2^30).
  */
 int dist_gibbs_set_option(dist_gibbs_t * g, const char * name, int value);
 /* how many batches each score+sample kernel has served */

@@ -15,9 +15,10 @@ import ctypes
 
 import numpy as np
 import pytest
-from scipy import special, stats
+from scipy import stats
 
 import oracle_lib as ol
+from f64_scores import float64_score
 
 TOL = 1e-3   # distributions/tests/util.py:42
 
@@ -50,44 +51,6 @@ EXAMPLES = [
 
 def words(kind, value):
     return int(ol.value_words(kind, [value])[0])
-
-
-def float64_score(kind, kw, group_values, value):
-    """log predictive density of `value` given the group's values, in float64
-    (what the dbg flavour computes with scipy)."""
-    v = np.asarray(group_values, np.float64)
-    n = len(v)
-    if kind == ol.DD:
-        a = np.asarray(kw["alphas"], np.float64)
-        c = np.bincount(np.asarray(group_values, int), minlength=len(a))
-        return np.log((a[value] + c[value]) / (a.sum() + n))
-    if kind == ol.DPD:
-        b = np.asarray(kw["betas"], np.float64) * kw["alpha"]
-        c = np.bincount(np.asarray(group_values, int), minlength=len(b))
-        return np.log((b[value] + c[value]) / (kw["alpha"] + n))
-    if kind == ol.BB:
-        h = v.sum()
-        a, b = kw["alpha"] + h, kw["beta"] + n - h
-        return np.log((a if value else b) / (a + b))
-    if kind == ol.GP:
-        a = kw["alpha"] + v.sum()
-        ib = kw["inv_beta"] + n
-        # negative binomial predictive
-        return (special.gammaln(a + value) - special.gammaln(a)
-                - special.gammaln(value + 1) + a * np.log(ib / (ib + 1.0))
-                - value * np.log(ib + 1.0))
-    if kind == ol.NICH:
-        mu, kappa, sigmasq, nu = (kw["mu"], kw["kappa"], kw["sigmasq"],
-                                  kw["nu"])
-        mean = v.mean() if n else 0.0
-        ctv = ((v - mean) ** 2).sum() if n else 0.0
-        kn = kappa + n
-        mun = (kappa * mu + mean * n) / kn
-        nun = nu + n
-        sn = (nu * sigmasq + ctv + n * kappa * (mu - mean) ** 2 / kn) / nun
-        scale = np.sqrt(sn * (kn + 1.0) / kn)
-        return stats.t.logpdf(value, nun, loc=mun, scale=scale)
-    raise ValueError(kind)
 
 
 @pytest.mark.parametrize("name,kind,kw,values", EXAMPLES)
