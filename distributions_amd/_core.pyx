@@ -258,6 +258,21 @@ cdef extern from "distributions_hip.h" nogil:
                                 uint64_t *, int)
     int dist_gibbs_set_option(dist_gibbs_t *, const char *, int)
     int dist_gibbs_path_counts(const dist_gibbs_t *, uint64_t *, uint64_t *)
+    int dist_gibbs_shared(const dist_gibbs_t *, int, dist_shared_t *)
+    int dist_gibbs_clustering(const dist_gibbs_t *, float *, float *)
+    int dist_gibbs_score_data(dist_gibbs_t *, float *, float *)
+    int dist_gibbs_score_data_grid(dist_gibbs_t *, int, const dist_shared_t *,
+                                   size_t, float *)
+    int dist_gibbs_score_counts_grid(dist_gibbs_t *, const float *,
+                                     const float *, size_t, float *)
+    int dist_gibbs_set_shared(dist_gibbs_t *, int, const dist_shared_t *)
+    int dist_gibbs_set_clustering(dist_gibbs_t *, float, float)
+    int dist_gibbs_sample_hypers(dist_gibbs_t *, int, const dist_shared_t *,
+                                 size_t, uint32_t *, size_t *)
+    int dist_gibbs_sample_clustering(dist_gibbs_t *, const float *,
+                                     const float *, size_t, uint32_t *,
+                                     size_t *)
+    int dist_gibbs_hyper_stats(dist_gibbs_t *, uint64_t *)
 
 
 KIND_DD = DIST_DD
@@ -1415,6 +1430,120 @@ cdef class GibbsEngine:
         check(dist_gibbs_kernel_stats(self.ptr, &ms, &launches, &rows,
                                       1 if reset else 0))
         return ms, launches, rows
+
+    # -- hyper-parameters (include/distributions_hip.h, "engine
+    # hyper-parameters") ------------------------------------------------------
+    def shared(self, int feature):
+        """-> SharedParams the engine currently runs feature `feature` under"""
+        cdef SharedParams given, out = SharedParams()
+        cdef cnp.ndarray[cnp.float32_t, ndim=1] b
+        if not 0 <= feature < len(self.shareds):
+            raise RuntimeError("ERROR shared: bad feature index")
+        given = self.shareds[feature]
+        if given.c.kind == DIST_DPD:
+            b = np.zeros(given.c.dim, np.float32)
+            out._betas = b
+            out.c.betas = <const float *> b.data
+        check(dist_gibbs_shared(self.ptr, feature, &out.c))
+        return out
+
+    def clustering(self):
+        """-> PitmanYor's (alpha, d)"""
+        cdef float alpha = 0, d = 0
+        check(dist_gibbs_clustering(self.ptr, &alpha, &d))
+        return alpha, d
+
+    def score_data(self):
+        """-> (float32 score_data per feature, score_counts of the clustering
+        model)"""
+        cdef cnp.ndarray[cnp.float32_t, ndim=1] out = np.zeros(
+            len(self.shareds) + 1, np.float32)
+        cdef float clustering = 0
+        check(dist_gibbs_score_data(self.ptr, <float *> out.data, &clustering))
+        return out[:len(self.shareds)].copy(), clustering
+
+    cdef dist_shared_t * _candidates(self, shareds) except NULL:
+        cdef size_t n = len(shareds)
+        cdef dist_shared_t * arr = <dist_shared_t *> malloc(
+            (n + 1) * sizeof(dist_shared_t))
+        cdef SharedParams s
+        cdef size_t i
+        try:
+            for i in range(n):
+                s = shareds[i]
+                arr[i] = s.c
+        except:
+            free(arr)
+            raise
+        return arr
+
+    def score_data_grid(self, int feature, shareds):
+        """shareds: SharedParams candidates for `feature` -> float32 scores"""
+        cdef size_t n = len(shareds)
+        cdef cnp.ndarray[cnp.float32_t, ndim=1] out = np.zeros(n, np.float32)
+        cdef dist_shared_t * arr = self._candidates(shareds)
+        cdef int rc
+        with nogil:
+            rc = dist_gibbs_score_data_grid(self.ptr, feature, arr, n,
+                                            <float *> out.data)
+        free(arr)
+        check(rc)
+        return out
+
+    def score_counts_grid(self, alphas, ds):
+        """-> float32 PitmanYor score_counts per (alphas[c], ds[c])"""
+        cdef cnp.ndarray[cnp.float32_t, ndim=1] a = np.ascontiguousarray(
+            alphas, dtype=np.float32)
+        cdef cnp.ndarray[cnp.float32_t, ndim=1] d = np.ascontiguousarray(
+            ds, dtype=np.float32)
+        if a.shape[0] != d.shape[0]:
+            raise ValueError("one d per alpha")
+        cdef cnp.ndarray[cnp.float32_t, ndim=1] out = np.zeros(a.shape[0],
+                                                               np.float32)
+        check(dist_gibbs_score_counts_grid(
+            self.ptr, <const float *> a.data, <const float *> d.data,
+            a.shape[0], <float *> out.data))
+        return out
+
+    def set_shared(self, int feature, SharedParams shared):
+        check(dist_gibbs_set_shared(self.ptr, feature, &shared.c))
+        self.shareds[feature] = shared
+
+    def set_clustering(self, float alpha, float d):
+        check(dist_gibbs_set_clustering(self.ptr, alpha, d))
+
+    def sample_hypers(self, int feature, shareds, uint32_t rng_state):
+        """grid + draw + install on the device -> (index, new rng state)"""
+        cdef size_t n = len(shareds), chosen = 0
+        cdef dist_shared_t * arr = self._candidates(shareds)
+        cdef int rc
+        with nogil:
+            rc = dist_gibbs_sample_hypers(self.ptr, feature, arr, n,
+                                          &rng_state, &chosen)
+        free(arr)
+        check(rc)
+        self.shareds[feature] = shareds[chosen]
+        return chosen, rng_state
+
+    def sample_clustering(self, alphas, ds, uint32_t rng_state):
+        """-> (index, new rng state); (alphas[index], ds[index]) installed"""
+        cdef cnp.ndarray[cnp.float32_t, ndim=1] a = np.ascontiguousarray(
+            alphas, dtype=np.float32)
+        cdef cnp.ndarray[cnp.float32_t, ndim=1] d = np.ascontiguousarray(
+            ds, dtype=np.float32)
+        if a.shape[0] != d.shape[0]:
+            raise ValueError("one d per alpha")
+        cdef size_t chosen = 0
+        check(dist_gibbs_sample_clustering(
+            self.ptr, <const float *> a.data, <const float *> d.data,
+            a.shape[0], &rng_state, &chosen))
+        return chosen, rng_state
+
+    def hyper_stats(self):
+        """-> (accumulator chains, candidates scored, launches, calls)"""
+        cdef uint64_t out[4]
+        check(dist_gibbs_hyper_stats(self.ptr, out))
+        return out[0], out[1], out[2], out[3]
 
 
 def sweep_sequential_many(engines, size_t row_begin, size_t row_end,

@@ -405,6 +405,34 @@ struct Slave {
     explicit Slave(const dist_shared_t & shared) : sh(shared) {
         check_shared(sh);
         ensure_device_ready();
+        install();
+    }
+    // dist_gibbs_set_shared: another Shared of the same kind and dim.  The
+    // statistics stay; everything derived from the hyper-parameters alone is
+    // built again, as the constructor builds it (the caller rebuilds the
+    // caches over the groups: init()).
+    void set_shared(const dist_shared_t & cand) {
+        DIST_REQUIRE(cand.kind == sh.kind, "set_shared: model mismatch");
+        DIST_REQUIRE(!is_cat(sh.kind) || cand.dim == sh.dim,
+                     "set_shared: dim mismatch");
+        check_shared(cand);
+        // (the candidate's betas may be the very array this feature holds)
+        std::vector<float> cand_betas;
+        if (cand.kind == DIST_DPD)
+            cand_betas.assign(cand.betas, cand.betas + cand.dim);
+        std::vector<float> held_before;
+        held_before.swap(held_lgamma);
+        sh = cand;
+        if (sh.kind == DIST_DPD) {
+            betas.swap(cand_betas);
+            sh.betas = betas.data();
+        }
+        memset(gp_lut, 0, sizeof(gp_lut));
+        install();   // (registers the new arguments before the old ones go)
+        release_small_lgamma(held_before);
+    }
+    // what follows from sh alone
+    void install() {
         if (sh.kind == DIST_GP) {
             // every float (alpha + s) + x with s + x <= 2, and glibc's lgammaf
             // of it (the call the reference makes, special.hpp:121-123)
@@ -710,6 +738,22 @@ struct Slave {
     void score_data_grid(const dist_shared_t * shareds, size_t n,
                          float * scores_out) const {
         if (!n) return;
+        DeviceBuf<float> out;
+        out.reserve(n, 0);
+        score_data_grid_dev(shareds, n, out.p, nullptr);
+        out.download(scores_out, n);
+    }
+    // accumulator chains run, candidates, launches (dist_gibbs_hyper_stats)
+    struct GridWork {
+        uint64_t chains = 0, candidates = 0, launches = 0;
+    };
+    // ... with the scores left on the device (out_dev[n], all written).
+    // `work` given: the engine's form, DirichletDiscrete's chains follow what
+    // changed between candidates (kernels_hyper.h).
+    void score_data_grid_dev(const dist_shared_t * shareds, size_t n,
+                             float * out_dev, GridWork * work) const {
+        if (!n) return;
+        if (work) work->candidates += n;
         const size_t dimc = is_cat(sh.kind) ? (size_t)sh.dim : 0;
         std::vector<float> cp(4 * n), cprior(std::max<size_t>(1, dimc * n)),
             csum(n, 0.f);
@@ -742,7 +786,7 @@ struct Slave {
             }
         }
         if (!K) {
-            for (size_t c = 0; c < n; ++c) scores_out[c] = 0.f;
+            HIP_CHECK(hipMemsetAsync(out_dev, 0, n * sizeof(float), stream()));
             return;
         }
         // glibc's lgammaf for the small arguments these candidates reach,
@@ -755,11 +799,16 @@ struct Slave {
             const std::vector<float> & ys;
             ~Release() { release_small_lgamma(ys); }
         } release_at_exit{grid_args};
+        SlaveView v = view();
+        if (sh.kind == DIST_DD && work) {
+            dd_chains(shareds, n, csum, out_dev, work);
+            return;
+        }
         DeviceBuf<float> dp, dprior, dsum;
         dp.upload(cp.data(), cp.size());
         dprior.upload(cprior.data(), cprior.size());
         dsum.upload(csum.data(), csum.size());
-        SlaveView v = view();
+        if (work) work->launches += sh.kind == DIST_DD ? 1 : 2;
         if (sh.kind == DIST_DPD) {
             // sparse-counter iteration order is not defined in the reference
             // (dpd.hpp:344-374): terms summed in binary64, 1e-5 relative
@@ -772,17 +821,14 @@ struct Slave {
                                dim3(kBlock), 0, stream(), v, dp.p, dprior.p,
                                dsum.p, out.p);
             HIP_CHECK(hipGetLastError());
-            std::vector<double> totals(n);
-            out.download(totals.data(), n);
-            for (size_t c = 0; c < n; ++c) scores_out[c] = (float)totals[c];
+            LAUNCH(k_hyper_narrow, n, out.p, (int)n, out_dev);
+            sync();   // (the candidate arrays are freed on return)
             return;
         }
         // the reference's float accumulation order, bit for bit
-        DeviceBuf<float> out;
-        out.reserve(n, 0);
         if (sh.kind == DIST_DD) {
             hipLaunchKernelGGL(k_score_data_dd, dim3((unsigned)n), dim3(512), 0,
-                               stream(), v, dprior.p, dsum.p, out.p);
+                               stream(), v, dprior.p, dsum.p, out_dev);
             HIP_CHECK(hipGetLastError());
         } else {
             DeviceBuf<float> terms;
@@ -793,10 +839,68 @@ struct Slave {
                                dim3(kBlock), 0, stream(), v, dp.p, terms.p);
             HIP_CHECK(hipGetLastError());
             hipLaunchKernelGGL(k_score_data_serial, dim3((unsigned)n), dim3(64),
-                               0, stream(), terms.p, (size_t)K * 4, out.p);
+                               0, stream(), terms.p, (size_t)K * 4, out_dev);
             HIP_CHECK(hipGetLastError());
         }
-        out.download(scores_out, n);
+        sync();   // (the candidate arrays are freed on return)
+    }
+    // DirichletDiscrete's grid as a job list (kernels_hyper.h): one chain per
+    // distinct (v, alphas[v]) and per distinct alpha_sum -- csum[c], carried
+    // in binary64 by the caller -- then the closing pass per candidate.
+    void dd_chains(const dist_shared_t * shareds, size_t n,
+                   const std::vector<float> & csum, float * out_dev,
+                   GridWork * work) const {
+        const int dim = sh.dim, width = dim + 1;
+        std::vector<HyperJob> jobs;
+        std::vector<int> pick(n * (size_t)width);
+        // (per coordinate the values met so far: grids are short, and a
+        // coordinate grid changes one of them)
+        std::vector<std::vector<std::pair<uint32_t, int>>> met((size_t)dim);
+        auto bits = [](float x) { uint32_t u; memcpy(&u, &x, 4); return u; };
+        for (size_t c = 0; c < n; ++c)
+            for (int v = 0; v < dim; ++v) {
+                const float a = shareds[c].alphas[v];
+                int & slot = pick[c * width + v];
+                if (c && bits(a) == bits(shareds[c - 1].alphas[v])) {
+                    slot = pick[(c - 1) * width + v];
+                    continue;
+                }
+                slot = -1;
+                for (auto & m : met[v])
+                    if (m.first == bits(a)) slot = m.second;
+                if (slot < 0) {
+                    slot = (int)jobs.size();
+                    jobs.push_back(HyperJob{a, v});
+                    met[v].emplace_back(bits(a), slot);
+                }
+            }
+        std::vector<std::pair<uint32_t, int>> sums;
+        for (size_t c = 0; c < n; ++c) {
+            int & slot = pick[c * width + dim];
+            slot = -1;
+            for (auto & m : sums)
+                if (m.first == bits(csum[c])) slot = m.second;
+            if (slot < 0) {
+                slot = (int)jobs.size();
+                jobs.push_back(HyperJob{csum[c], dim});
+                sums.emplace_back(bits(csum[c]), slot);
+            }
+        }
+        DeviceBuf<HyperJob> djobs;
+        DeviceBuf<int> dpick;
+        DeviceBuf<float> vals;
+        djobs.upload(jobs.data(), jobs.size());
+        dpick.upload(pick.data(), pick.size());
+        vals.reserve(jobs.size(), 0);
+        hipLaunchKernelGGL(k_hyper_dd_chains,
+                           dim3((unsigned)((jobs.size() + 63) / 64)), dim3(64),
+                           0, stream(), view(), djobs.p, (int)jobs.size(),
+                           vals.p);
+        HIP_CHECK(hipGetLastError());
+        LAUNCH(k_hyper_dd_close, n, dpick.p, vals.p, width, (int)n, out_dev);
+        work->chains += jobs.size();
+        work->launches += 2;
+        sync();   // (the job list is freed on return)
     }
     // score_value for n values at once: acc[r * ld + k] accumulates
     void score_values(const uint32_t * vals, size_t n, float * acc,
@@ -1385,6 +1489,7 @@ struct Gibbs {
         }
         if (peek_pending) (void)hipEventSynchronize(peek_event);
         if (peek_event) (void)hipEventDestroy(peek_event);
+        if (pinned_draw) (void)hipHostFree(pinned_draw);
         if (pinned_state) (void)hipHostFree(pinned_state);
         if (pinned_counts) (void)hipHostFree(pinned_counts);
         if (pinned_seq) (void)hipHostFree(pinned_seq);
@@ -1681,6 +1786,176 @@ struct Gibbs {
         py.rebuild(alpha, d);
         for (auto & s : feats) s->init();
     }
+    // ---- the hyper-parameter step: score grids of candidates against the
+    // resident statistics, draw one on the device, install it
+    // (include/distributions_hip.h, "engine hyper-parameters")
+    Slave::GridWork hyper_work;
+    uint64_t hyper_calls = 0;
+    DeviceBuf<float> hyper_scores;
+    HyperDraw * pinned_draw = nullptr;
+
+    Slave & hyper_feature(int f, const char * what) const {
+        DIST_REQUIRE(f >= 0 && f < F(),
+                     std::string(what) + ": bad feature index");
+        return *feats[(size_t)f];
+    }
+    void hyper_enter(const char * what, bool reads_cells) {
+        DIST_REQUIRE(!batch_open, std::string(what) + ": a batch is open");
+        if (reads_cells) require_whole(what);
+        hyper_calls += 1;
+    }
+    static void check_clustering(float alpha_, float d_) {
+        DIST_REQUIRE(alpha_ > 0.f && d_ >= 0.f && d_ < 1.f,
+                     "expected alpha > 0, 0 <= d < 1");
+    }
+    void get_shared(int f, dist_shared_t * out) const {
+        const Slave & s = hyper_feature(f, "shared");
+        const float * callers = out->betas;
+        DIST_REQUIRE(s.sh.kind != DIST_DPD || callers != nullptr,
+                     "shared: a DirichletProcessDiscrete feature needs "
+                     "out->betas to point at dim floats");
+        *out = s.sh;
+        out->betas = nullptr;
+        if (s.sh.kind == DIST_DPD) {
+            memcpy(const_cast<float *>(callers), s.betas.data(),
+                   sizeof(float) * (size_t)s.sh.dim);
+            out->betas = callers;
+        }
+    }
+    // PitmanYor::score_counts (clustering.cc:152-183) of the engine's group
+    // sizes under every (alphas[c], ds[c]); the scores stay on the device
+    void score_counts_grid_dev(const float * alphas, const float * ds, size_t n,
+                               float * out_dev) {
+        DIST_REQUIRE(cluster == 0, "score_counts_grid: a LowEntropy engine "
+                                   "has no (alpha, d) to score");
+        if (!n) return;
+        for (size_t c = 0; c < n; ++c) check_clustering(alphas[c], ds[c]);
+        hyper_work.candidates += n;
+        const size_t Kn = (size_t)K();
+        if (!Kn) {
+            HIP_CHECK(hipMemsetAsync(out_dev, 0, n * sizeof(float), stream()));
+            return;
+        }
+        std::vector<unsigned long long> before(2 * Kn);
+        unsigned long long ne = 0, rows = 0;
+        for (size_t k = 0; k < Kn; ++k) {
+            before[2 * k] = ne;
+            before[2 * k + 1] = rows;
+            if (py.counts[k]) {
+                ne += 1;
+                rows += (unsigned long long)py.counts[k];
+            }
+        }
+        DeviceBuf<unsigned long long> b;
+        DeviceBuf<float> da, dd;
+        b.upload(before.data(), before.size());
+        da.upload(alphas, n);
+        dd.upload(ds, n);
+        hipLaunchKernelGGL(k_hyper_py_grid, dim3((unsigned)n),
+                           dim3(kHyperCountsBlock), 0, stream(), py.d_counts.p,
+                           b.p, (int)Kn, da.p, dd.p, out_dev);
+        HIP_CHECK(hipGetLastError());
+        hyper_work.launches += 1;
+        sync();   // (the candidate arrays are freed on return)
+    }
+    void score_data_grid(int f, const dist_shared_t * shareds, size_t n,
+                         float * scores_out) {
+        hyper_enter("score_data_grid", true);
+        const Slave & s = hyper_feature(f, "score_data_grid");
+        if (!n) return;
+        hyper_scores.reserve(n, 0);
+        s.score_data_grid_dev(shareds, n, hyper_scores.p, &hyper_work);
+        hyper_scores.download(scores_out, n);
+    }
+    void score_counts_grid(const float * alphas, const float * ds, size_t n,
+                           float * scores_out) {
+        hyper_enter("score_counts_grid", false);
+        if (!n) return;
+        hyper_scores.reserve(n, 0);
+        score_counts_grid_dev(alphas, ds, n, hyper_scores.p);
+        hyper_scores.download(scores_out, n);
+    }
+    // MixtureSlave::score_data per feature (mixture.hpp:427-431) and
+    // PitmanYor's score_counts (a LowEntropy engine's: dist_gibbs_score_data)
+    void score_data(float * per_feature, float * clustering) {
+        hyper_enter("score_data", true);
+        const size_t nf = (size_t)F();
+        hyper_scores.reserve(nf + 1, 0);
+        for (size_t f = 0; f < nf; ++f)
+            feats[f]->score_data_grid_dev(&feats[f]->sh, 1, hyper_scores.p + f,
+                                          &hyper_work);
+        if (cluster == 0)
+            score_counts_grid_dev(&alpha, &d, 1, hyper_scores.p + nf);
+        std::vector<float> got(nf + 1, 0.f);
+        hyper_scores.download(got.data(), nf + 1);
+        for (size_t f = 0; f < nf; ++f) per_feature[f] = got[f];
+        *clustering = got[nf];
+    }
+    // Everything derived from the hyper-parameters is a function of them and
+    // of the statistics: the feature's own tables (Slave::set_shared), then
+    // the caches over the groups and what the next batch or chain builds from
+    // them (base[], the per-value tables: rebuild_caches, as after an import
+    // of statistics).  The statistics, the rows and the id maps stay.
+    void set_shared(int f, const dist_shared_t * cand) {
+        hyper_enter("set_shared", false);
+        hyper_feature(f, "set_shared").set_shared(*cand);
+        rebuild_caches();
+        sync();
+    }
+    void set_clustering(float alpha_, float d_) {
+        hyper_enter("set_clustering", false);
+        DIST_REQUIRE(cluster == 0, "set_clustering: a LowEntropy engine has no "
+                                   "(alpha, d) to set");
+        check_clustering(alpha_, d_);
+        alpha = alpha_;
+        d = d_;
+        rebuild_caches();
+        sync();
+    }
+    // sample_from_scores_overwrite over hyper_scores[0..n): one engine step
+    size_t hyper_draw(size_t n, uint32_t * rng_state) {
+        if (!pinned_draw)
+            HIP_CHECK(hipHostMalloc((void **)&pinned_draw, sizeof(HyperDraw),
+                                    hipHostMallocDefault));
+        pinned_draw->index = ~0u;
+        LAUNCH1(k_hyper_draw, hyper_scores.p, (int)n, *rng_state, pinned_draw);
+        hyper_work.launches += 1;
+        sync();
+        DIST_REQUIRE(pinned_draw->index < n, "internal: the draw did not land");
+        *rng_state = pinned_draw->rng_state;
+        return (size_t)pinned_draw->index;
+    }
+    void sample_hypers(int f, const dist_shared_t * shareds, size_t n,
+                       uint32_t * rng_state, size_t * chosen) {
+        hyper_enter("sample_hypers", true);
+        Slave & s = hyper_feature(f, "sample_hypers");
+        DIST_REQUIRE(n > 0, "sample_hypers: expected 0 < size");
+        DIST_REQUIRE(n <= 0x7FFFFFFFu, "sample_hypers: too many candidates");
+        hyper_scores.reserve(n, 0);
+        s.score_data_grid_dev(shareds, n, hyper_scores.p, &hyper_work);
+        const size_t pick = hyper_draw(n, rng_state);
+        s.set_shared(shareds[pick]);
+        rebuild_caches();
+        sync();
+        *chosen = pick;
+    }
+    void sample_clustering(const float * alphas, const float * ds, size_t n,
+                           uint32_t * rng_state, size_t * chosen) {
+        hyper_enter("sample_clustering", false);
+        DIST_REQUIRE(cluster == 0, "sample_clustering: a LowEntropy engine has "
+                                   "no (alpha, d) to set");
+        DIST_REQUIRE(n > 0, "sample_clustering: expected 0 < size");
+        DIST_REQUIRE(n <= 0x7FFFFFFFu, "sample_clustering: too many candidates");
+        hyper_scores.reserve(n, 0);
+        score_counts_grid_dev(alphas, ds, n, hyper_scores.p);
+        const size_t pick = hyper_draw(n, rng_state);
+        alpha = alphas[pick];
+        d = ds[pick];
+        rebuild_caches();
+        sync();
+        *chosen = pick;
+    }
+
     // The group sizes are final once a batch's integer statistics are applied;
     // the ordered replay of its float statistics (C3: 0.26 of 2.2 ms) does
     // not touch them.  Published BEFORE the replay, they are on the host when
@@ -6001,6 +6276,89 @@ int dist_gibbs_get_group(const dist_gibbs_t * g, int feature, size_t groupid,
         g->impl.read()->require_whole("get_group");
         dist::sync();
         g->impl.read()->feats[feature]->get_group(groupid, group_out);
+    });
+}
+// ---- engine hyper-parameters ------------------------------------------------
+// (readers come through impl.read(): a run this rank closed stays resumable;
+// set_* and sample_* through impl->, which forgets it)
+int dist_gibbs_shared(const dist_gibbs_t * g, int feature,
+                      dist_shared_t * out) {
+    return guarded([&] {
+        DIST_REQUIRE(out, "null argument");
+        g->impl.read()->get_shared(feature, out);
+    });
+}
+int dist_gibbs_clustering(const dist_gibbs_t * g, float * alpha, float * d) {
+    return guarded([&] {
+        DIST_REQUIRE(alpha && d, "null argument");
+        const Gibbs * e = g->impl.read();
+        DIST_REQUIRE(e->cluster == 0, "clustering: a LowEntropy engine has no "
+                                      "(alpha, d)");
+        *alpha = e->alpha;
+        *d = e->d;
+    });
+}
+int dist_gibbs_score_data(dist_gibbs_t * g, float * per_feature,
+                          float * clustering) {
+    return guarded([&] {
+        DIST_REQUIRE(clustering && (per_feature || !g->impl.open()->F()),
+                     "null argument");
+        Gibbs * e = g->impl.read();
+        e->score_data(per_feature, clustering);
+        if (e->cluster != 0)
+            *clustering = le_score_counts(e->dataset_size, e->py.counts.data(),
+                                          e->py.counts.size());
+    });
+}
+int dist_gibbs_score_data_grid(dist_gibbs_t * g, int feature,
+                               const dist_shared_t * shareds, size_t n,
+                               float * scores_out) {
+    return guarded([&] {
+        DIST_REQUIRE(n == 0 || (shareds && scores_out), "null argument");
+        g->impl.read()->score_data_grid(feature, shareds, n, scores_out);
+    });
+}
+int dist_gibbs_score_counts_grid(dist_gibbs_t * g, const float * alphas,
+                                 const float * ds, size_t n,
+                                 float * scores_out) {
+    return guarded([&] {
+        DIST_REQUIRE(n == 0 || (alphas && ds && scores_out), "null argument");
+        g->impl.read()->score_counts_grid(alphas, ds, n, scores_out);
+    });
+}
+int dist_gibbs_set_shared(dist_gibbs_t * g, int feature,
+                          const dist_shared_t * shared) {
+    return guarded([&] {
+        DIST_REQUIRE(shared, "null argument");
+        g->impl->set_shared(feature, shared);
+    });
+}
+int dist_gibbs_set_clustering(dist_gibbs_t * g, float alpha, float d) {
+    return guarded([&] { g->impl->set_clustering(alpha, d); });
+}
+int dist_gibbs_sample_hypers(dist_gibbs_t * g, int feature,
+                             const dist_shared_t * shareds, size_t n,
+                             uint32_t * rng_state, size_t * chosen) {
+    return guarded([&] {
+        DIST_REQUIRE(shareds && rng_state && chosen, "null argument");
+        g->impl->sample_hypers(feature, shareds, n, rng_state, chosen);
+    });
+}
+int dist_gibbs_sample_clustering(dist_gibbs_t * g, const float * alphas,
+                                 const float * ds, size_t n,
+                                 uint32_t * rng_state, size_t * chosen) {
+    return guarded([&] {
+        DIST_REQUIRE(alphas && ds && rng_state && chosen, "null argument");
+        g->impl->sample_clustering(alphas, ds, n, rng_state, chosen);
+    });
+}
+int dist_gibbs_hyper_stats(dist_gibbs_t * g, uint64_t out[4]) {
+    return guarded([&] {
+        const Gibbs * e = g->impl.open();   // (counters only)
+        out[0] = e->hyper_work.chains;
+        out[1] = e->hyper_work.candidates;
+        out[2] = e->hyper_work.launches;
+        out[3] = e->hyper_calls;
     });
 }
 int dist_gibbs_packed_to_global(const dist_gibbs_t * g, uint32_t packed,

@@ -18,3 +18,4 @@ constexpr int kMaxF = DIST_MAX_FEATURES;
 #include "kernels_rows.h"
 #include "kernels_vs.h"
 #include "kernels_apply.h"
+#include "kernels_hyper.h"

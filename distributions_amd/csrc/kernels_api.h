@@ -39,9 +39,8 @@ struct SampleOut {
 
 // mode 0: scores_to_likelihoods; 1: + sample (u given); 2: log_sum_exp only;
 // 3: sample from given likelihoods/total
-__global__ void k_sample_scalar(int mode, int n, float * __restrict__ scores,
-                                float total_in, float u, SampleOut * out) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+__device__ inline void sample_scalar(int mode, int n, float * __restrict__ scores,
+                                     float total_in, float u, SampleOut * out) {
     float total = total_in;
     if (mode != 3) {
         float m = scores[0];
@@ -67,6 +66,11 @@ __global__ void k_sample_scalar(int mode, int n, float * __restrict__ scores,
         }
     }
     out->sample = sample;
+}
+__global__ void k_sample_scalar(int mode, int n, float * __restrict__ scores,
+                                float total_in, float u, SampleOut * out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    sample_scalar(mode, n, scores, total_in, u, out);
 }
 
 // ---------------------------------------------------------------------------

@@ -134,6 +134,50 @@ class Gibbs(object):
     def row_scores(self, row):
         return self.core.row_scores(row)
 
+    # -- hyper-parameters ---------------------------------------------------
+    # The step the reference alternates with assignment sweeps
+    # (mixture.hpp:427-438, then sample_from_scores and init()), on the
+    # statistics the engine holds.  Scoring closes an open run but changes
+    # nothing; set_* and sample_* install new values and rebuild what is
+    # derived from them.  self.shareds, self.alpha and self.d follow.
+    def score_data(self):
+        """-> (score_data per feature, score_counts of the clustering model)"""
+        return self.core.score_data()
+
+    def score_data_grid(self, feature, shareds):
+        """score_data of `feature` under each candidate Shared"""
+        return self.core.score_data_grid(feature, list(shareds))
+
+    def score_counts_grid(self, alphas, ds):
+        """PitmanYor score_counts under each (alphas[c], ds[c])"""
+        return self.core.score_counts_grid(alphas, ds)
+
+    def set_shared(self, feature, shared):
+        self.core.set_shared(feature, shared)
+        self.shareds[feature] = shared
+
+    def set_clustering(self, alpha, d):
+        self.core.set_clustering(alpha, d)
+        self.alpha, self.d = self.core.clustering()
+
+    def sample_hypers(self, feature, shareds, rng_state):
+        """Score the grid, draw one candidate with one engine step, install
+        it -- all on the device.  -> (index, new rng state)"""
+        shareds = list(shareds)
+        index, rng_state = self.core.sample_hypers(feature, shareds, rng_state)
+        self.shareds[feature] = shareds[index]
+        return index, rng_state
+
+    def sample_clustering(self, alphas, ds, rng_state):
+        """-> (index, new rng state); (alphas[index], ds[index]) installed"""
+        index, rng_state = self.core.sample_clustering(alphas, ds, rng_state)
+        self.alpha, self.d = self.core.clustering()
+        return index, rng_state
+
+    def hyper_stats(self):
+        """(accumulator chains, candidates scored, launches, calls)"""
+        return self.core.hyper_stats()
+
     def kernel_stats(self, reset=False):
         return self.core.kernel_stats(reset)
 
@@ -371,6 +415,7 @@ class ShardedGibbs(object):
         if self._comm is None:
             raise RuntimeError("partition_by_value needs use_native_comm()")
         self.backend.partition_by_value(self._comm)
+        self._partitioned = True
 
     def gather_cells(self):
         """Collective: the replicas of value-partitioned ranks are whole again
@@ -380,6 +425,38 @@ class ShardedGibbs(object):
     @property
     def native_comm(self):
         return self._comm
+
+    # -- hyper-parameters: every rank calls these alike.  The scoring ones
+    # read every cell, so value-partitioned ranks gather theirs first; with
+    # equal rng_state the replicas choose the same index, because their
+    # statistics are equal.
+    def _whole(self):
+        if self._comm is not None and getattr(self, "_partitioned", False):
+            self.backend.gather_cells(self._comm)
+
+    def score_data(self):
+        self._whole()
+        return self.backend.score_data()
+
+    def score_data_grid(self, feature, shareds):
+        self._whole()
+        return self.backend.score_data_grid(feature, list(shareds))
+
+    def score_counts_grid(self, alphas, ds):
+        return self.backend.score_counts_grid(alphas, ds)
+
+    def set_shared(self, feature, shared):
+        self.backend.set_shared(feature, shared)
+
+    def set_clustering(self, alpha, d):
+        self.backend.set_clustering(alpha, d)
+
+    def sample_hypers(self, feature, shareds, rng_state):
+        self._whole()
+        return self.backend.sample_hypers(feature, list(shareds), rng_state)
+
+    def sample_clustering(self, alphas, ds, rng_state):
+        return self.backend.sample_clustering(alphas, ds, rng_state)
 
     def sweep(self, batch_rows, seed_state, draw_base=0):
         """One pass over the local shard; all ranks take the same number of

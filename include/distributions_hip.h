@@ -715,6 +715,98 @@ int dist_gibbs_kernel_stats(dist_gibbs_t * g, double * ms_out,
                             uint64_t * launches_out, uint64_t * rows_out,
                             int reset);
 
+/* ---- engine hyper-parameters -------------------------------------------
+ * The reference's mixture interface alternates assignment sweeps
+ * (mixture.hpp:73-122) with a hyper-parameter step: score a grid of candidate
+ * Shareds against the groups (MixtureSlave::score_data_grid), draw one
+ * (sample_from_scores), install it and init().  These entry points are that
+ * step on the statistics the engine holds: nothing is pulled to the host, no
+ * second mixture is built, the rows and id maps stay where they are.
+ *
+ * Two rules hold for all of them:
+ *  - dist_gibbs_shared, dist_gibbs_clustering, dist_gibbs_score_data,
+ *    dist_gibbs_score_data_grid and dist_gibbs_score_counts_grid are READERS.
+ *    They close an open device-normalised run but leave a sharded run this
+ *    rank closed resumable.  The scoring ones read every cell of the feature:
+ *    on a value-partitioned rank whose cells are stale they fail ("... are
+ *    stale on a value-partitioned rank") until dist_gibbs_gather_cells.
+ *  - dist_gibbs_set_* and dist_gibbs_sample_* are NOT readers: they close the
+ *    run and forget it.  On sharded engines every rank issues them alike;
+ *    replicas that call dist_gibbs_sample_* with equal rng_state choose the
+ *    same index, because their statistics are equal (DirichletProcessDiscrete
+ *    excepted: its binary64 sums are formed by atomics, see below).
+ * All of them fail while a batch is open (between dist_gibbs_batch_sample and
+ * dist_gibbs_batch_finish). */
+
+/* Model::Shared of one feature as the engine currently runs under it (the
+ * constructor argument, or what dist_gibbs_set_shared / dist_gibbs_sample_
+ * hypers installed since).  DirichletProcessDiscrete: out->betas must point at
+ * dim floats owned by the caller, which are written. */
+int dist_gibbs_shared(const dist_gibbs_t * g, int feature,
+                      dist_shared_t * out);
+/* PitmanYor's (alpha, d); fails on a LowEntropy engine */
+int dist_gibbs_clustering(const dist_gibbs_t * g, float * alpha, float * d);
+/* MixtureSlave::score_data (mixture.hpp:427-431) of every feature --
+ * per_feature[n_features] -- and score_counts of the engine's clustering
+ * model over its group sizes: PitmanYor::score_counts (clustering.cc:152-183),
+ * or LowEntropy::score_counts (clustering.cc:229-248) for an engine of
+ * dist_gibbs_create_low_entropy */
+int dist_gibbs_score_data(dist_gibbs_t * g, float * per_feature,
+                          float * clustering);
+/* MixtureSlave::score_data_grid (mixture.hpp:433-438, 238-247; dd.hpp:259-284)
+ * on the resident statistics: scores_out[c] = score_data under shareds[c].
+ * Kind and dim of every candidate are the feature's.  The float contract is
+ * dist_mixture_score_data_grid's: DirichletDiscrete and the scalar kinds in
+ * the reference's float accumulation order, bit for bit (DirichletDiscrete's
+ * alpha_sum carried in binary64 from candidate to candidate over the changed
+ * coordinates); DirichletProcessDiscrete in binary64, 1e-5 relative.
+ * DirichletDiscrete's work follows what changed: one accumulator chain per
+ * distinct (coordinate, alpha) and per distinct alpha_sum of the grid, so a
+ * coordinate grid of n candidates costs dim + 1 + 2 (n - 1) chains, not
+ * n (dim + 1). */
+int dist_gibbs_score_data_grid(dist_gibbs_t * g, int feature,
+                               const dist_shared_t * shareds, size_t n,
+                               float * scores_out);
+/* PitmanYor::score_counts (clustering.cc:152-183) of the engine's group sizes
+ * under every (alphas[c], ds[c]).  Fails on a LowEntropy engine, whose model
+ * has no such parameters. */
+int dist_gibbs_score_counts_grid(dist_gibbs_t * g, const float * alphas,
+                                 const float * ds, size_t n,
+                                 float * scores_out);
+/* Shared = candidate; init() (mixture.hpp:354-359).  The candidate is checked
+ * first (kind and dim unchanged, and what dist_gibbs_create checks); a refused
+ * candidate leaves the engine as it was.  Then everything derived from the
+ * hyper-parameters is rebuilt: the feature's prior tables and registered small
+ * lgamma arguments, the caches over the groups, and with them what the next
+ * batch or chain builds (per-value tables, base scores).  From then on the
+ * engine is indistinguishable from one created with the new values and handed
+ * the same groups, sizes and id maps; the sufficient statistics -- the
+ * order-dependent ones included -- do not depend on the hyper-parameters and
+ * stay as they are. */
+int dist_gibbs_set_shared(dist_gibbs_t * g, int feature,
+                          const dist_shared_t * shared);
+/* the same for PitmanYor's (alpha, d) (clustering.hpp:151-161); fails on a
+ * LowEntropy engine */
+int dist_gibbs_set_clustering(dist_gibbs_t * g, float alpha, float d);
+/* The whole step: the grid as in dist_gibbs_score_data_grid, then
+ * sample_from_scores_overwrite (random.hpp:361-392) on the device with ONE
+ * engine step from *rng_state, then dist_gibbs_set_shared of the chosen
+ * candidate.  Only *chosen and the advanced *rng_state cross the bus; the
+ * scores never do.  n > 0. */
+int dist_gibbs_sample_hypers(dist_gibbs_t * g, int feature,
+                             const dist_shared_t * shareds, size_t n,
+                             uint32_t * rng_state, size_t * chosen);
+/* ... and for the clustering model: dist_gibbs_score_counts_grid, the draw,
+ * dist_gibbs_set_clustering */
+int dist_gibbs_sample_clustering(dist_gibbs_t * g, const float * alphas,
+                                 const float * ds, size_t n,
+                                 uint32_t * rng_state, size_t * chosen);
+/* since creation: out[0] = accumulator chains run by DirichletDiscrete grids,
+ * out[1] = candidates scored, out[2] = kernel launches of this section,
+ * out[3] = calls of its scoring, set and sample entry points (does not close
+ * a run) */
+int dist_gibbs_hyper_stats(dist_gibbs_t * g, uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif
