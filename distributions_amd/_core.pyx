@@ -226,6 +226,12 @@ cdef extern from "distributions_hip.h" nogil:
     int dist_gibbs_row_scores(dist_gibbs_t *, size_t, float *, size_t *)
     int dist_gibbs_score_rows_dev(dist_gibbs_t *, size_t, size_t, float *,
                                   size_t)
+    int dist_gibbs_predict_dev(dist_gibbs_t *, size_t,
+                               const uint32_t * const *, float *, uint32_t *,
+                               int, uint32_t, uint64_t, float *)
+    int dist_gibbs_predict(dist_gibbs_t *, size_t, const uint32_t * const *,
+                           float *, uint32_t *, int, uint32_t, uint64_t,
+                           float *)
     size_t dist_gibbs_group_count(const dist_gibbs_t *)
     size_t dist_gibbs_row_count(const dist_gibbs_t *)
     int dist_gibbs_counts(const dist_gibbs_t *, int *)
@@ -1303,6 +1309,74 @@ cdef class GibbsEngine:
                        size_t ld):
         check(dist_gibbs_score_rows_dev(self.ptr, row_begin, row_end,
                                         <float *> ptr, ld))
+
+    def predict_dev(self, value_ptrs, size_t n_rows, size_t logp_ptr,
+                    size_t group_ptr, int mode, uint32_t seed_state,
+                    draw_base=0):
+        """Held-out rows (dist_gibbs_predict_dev): value_ptrs are device
+        addresses of one column of n_rows words per feature, logp_ptr /
+        group_ptr device addresses or 0.  -> log_sum_exp of the clustering
+        model's scores alone"""
+        cdef int n = len(self.shareds)
+        if len(value_ptrs) != n:
+            raise RuntimeError("one value column per feature")
+        cdef const uint32_t ** ptrs = <const uint32_t **> malloc(
+            sizeof(void *) * (n + 1))
+        cdef int i
+        cdef size_t addr
+        for i in range(n):
+            addr = value_ptrs[i]
+            ptrs[i] = <const uint32_t *> addr
+        cdef uint64_t db = <uint64_t> draw_base
+        cdef float total = 0
+        cdef int rc
+        with nogil:
+            rc = dist_gibbs_predict_dev(self.ptr, n_rows, ptrs,
+                                        <float *> logp_ptr,
+                                        <uint32_t *> group_ptr, mode,
+                                        seed_state, db, &total)
+        free(ptrs)
+        check(rc)
+        return total
+
+    def predict(self, values, mode, uint32_t seed_state, draw_base=0):
+        """Held-out rows from host arrays (dist_gibbs_predict): values is one
+        array per feature; mode 0 draws, 1 takes the first maximum, None
+        leaves the groups out.  -> (logp, groups or None, prior_total)"""
+        cdef int n = len(self.shareds)
+        if len(values) != n:
+            raise RuntimeError("one value column per feature")
+        cdef const uint32_t ** ptrs = <const uint32_t **> malloc(
+            sizeof(void *) * (n + 1))
+        cdef cnp.ndarray[cnp.uint32_t, ndim=1] w
+        cdef SharedParams s
+        words = []
+        cdef int i
+        cdef size_t rows = 0
+        for i in range(n):
+            s = self.shareds[i]
+            w = value_words(s.c.kind, values[i])
+            if i and w.shape[0] != rows:
+                free(ptrs)
+                raise RuntimeError("feature columns differ in length")
+            rows = w.shape[0]
+            words.append(w)
+            ptrs[i] = <const uint32_t *> w.data
+        cdef cnp.ndarray[cnp.float32_t, ndim=1] logp = np.zeros(
+            rows, np.float32)
+        cdef cnp.ndarray[cnp.uint32_t, ndim=1] group = np.zeros(
+            rows, np.uint32)
+        cdef uint32_t * gp = NULL if mode is None else <uint32_t *> group.data
+        cdef int m = 0 if mode is None else mode
+        cdef uint64_t db = <uint64_t> draw_base
+        cdef float total = 0
+        cdef int rc
+        with nogil:
+            rc = dist_gibbs_predict(self.ptr, rows, ptrs, <float *> logp.data,
+                                    gp, m, seed_state, db, &total)
+        free(ptrs)
+        check(rc)
+        return logp, (None if mode is None else group), total
 
     def group_count(self):
         return checked_size(dist_gibbs_group_count(self.ptr))

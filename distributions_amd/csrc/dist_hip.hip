@@ -2216,8 +2216,8 @@ struct Gibbs {
         if (nv * (size_t)K() > ((size_t)256 << 20)) return 0;   // > 1 GiB
         return (int)nv;
     }
-    // with_ktab = false: only tables that cost next to nothing are built
-    void prepare(SweepParams & P, bool with_ktab = true) {
+    // base[], base_single[] and the scalars (no gather tables)
+    void prepare_base(SweepParams & P) {
         base.reserve(grow_capacity((size_t)K()), 0);
         base_single.reserve(grow_capacity((size_t)K()), 0);
         P.base = base.p;
@@ -2227,6 +2227,10 @@ struct Gibbs {
                    scalars.p);
             base_valid = true;
         }
+    }
+    // with_ktab = false: only tables that cost next to nothing are built
+    void prepare(SweepParams & P, bool with_ktab = true) {
+        prepare_base(P);
         ktab.resize((size_t)F());
         for (int f = 0; f < F(); ++f) {
             int nv = ktab_values(f);
@@ -4863,6 +4867,80 @@ struct Gibbs {
                    out_dev + (c0 - r0) * ld, ld);
         }
     }
+
+    // Held-out rows (kernels_predict.h): one lane per query row, launched in
+    // chunks of at most this many whole rows (debug.predict_chunk lowers it)
+    size_t predict_chunk = (size_t)1 << 22;
+    DeviceBuf<float> predict_prior;
+    DeviceBuf<SampleOut> predict_total;
+    DeviceBuf<unsigned long long> predict_bad;
+    struct PredictLaunch {
+        const SweepParams * P;
+        const PredictArgs * A;
+        template <int KA, int KB, int NF>
+        void run() {
+            hipLaunchKernelGGL((k_predict<KA, KB, NF>), grid_for(P->row_end),
+                               dim3(kBlock), 0, stream(), *P, *A);
+            HIP_CHECK(hipGetLastError());
+        }
+    };
+    void predict(size_t n, const uint32_t * const * values_dev,
+                 float * logp_dev, uint32_t * group_dev, int mode,
+                 uint32_t seed_state, uint64_t draw_base,
+                 float * prior_total_out) {
+        DIST_REQUIRE(mode == 0 || mode == 1,
+                     "predict: mode is 0 (draw) or 1 (first maximum)");
+        // the caches it reads are the frozen state's only between batches
+        DIST_REQUIRE(!batch_open, "batch open");
+        require_whole("predict");
+        if (n == 0) return;
+        DIST_REQUIRE(values_dev != nullptr || F() == 0, "null argument");
+        for (int f = 0; f < F(); ++f)
+            DIST_REQUIRE(values_dev[f] != nullptr, "null value column");
+        upload_maps();
+        const size_t step = std::min(n, predict_chunk);
+        ensure_pow_tables(step);
+        SweepParams P = params(0, 0, seed_state, draw_base);
+        prepare_base(P);
+        const size_t Kn = (size_t)K();
+        predict_prior.reserve(grow_capacity(Kn), 0);
+        LAUNCH(k_predict_prior, Kn, P, predict_prior.p);
+        if (prior_total_out) {
+            // log_sum_exp of the driver's scores alone (random.cc:78-92)
+            predict_total.reserve(1, 0);
+            LAUNCH1(k_sample_scalar, 2, (int)Kn, predict_prior.p, 0.f, 0.f,
+                    predict_total.p);
+        }
+        predict_bad.reserve(1, 0);
+        HIP_CHECK(hipMemsetAsync(predict_bad.p, 0xFF, sizeof(unsigned long long),
+                                 stream()));
+        for (size_t c0 = 0; c0 < n; c0 += step) {
+            const size_t c1 = std::min(n, c0 + step);
+            for (int f = 0; f < F(); ++f) P.values[f] = values_dev[f] + c0;
+            P.row_begin = 0;
+            P.row_end = c1 - c0;
+            // row q draws with engine step draw_base + q + 1 of seed_state,
+            // whatever the chunking (the batch's own convention)
+            P.seed_batch = lcg_jump(seed_state, draw_base + c0 + 1ull);
+            const PredictArgs A = {predict_prior.p, d_p2g_ptr,
+                                   logp_dev ? logp_dev + c0 : nullptr,
+                                   group_dev ? group_dev + c0 : nullptr, mode,
+                                   (unsigned long long)c0, predict_bad.p};
+            PredictLaunch L{&P, &A};
+            dispatch(L);
+        }
+        unsigned long long bad = 0;
+        predict_bad.download(&bad, 1);   // (waits for the work)
+        if (prior_total_out) {
+            SampleOut out;
+            predict_total.download(&out, 1);
+            *prior_total_out = out.log_sum_exp;
+        }
+        DIST_REQUIRE(bad == ~0ull,
+                     "predict: value outside its feature's domain at row "
+                         + std::to_string(bad >> 8) + ", feature "
+                         + std::to_string(bad & 0xFF));
+    }
 };
 
 }  // namespace dist
@@ -6242,6 +6320,42 @@ int dist_gibbs_score_rows_dev(dist_gibbs_t * g, size_t row_begin,
         dist::sync();
     });
 }
+int dist_gibbs_predict_dev(dist_gibbs_t * g, size_t n_rows,
+                           const uint32_t * const * values_dev,
+                           float * logp_dev, uint32_t * group_dev, int mode,
+                           uint32_t seed_state, uint64_t draw_base,
+                           float * prior_total_out) {
+    return guarded([&] {
+        g->impl.read()->predict(n_rows, values_dev, logp_dev, group_dev, mode,
+                                seed_state, draw_base, prior_total_out);
+    });
+}
+int dist_gibbs_predict(dist_gibbs_t * g, size_t n_rows,
+                       const uint32_t * const * values, float * logp_out,
+                       uint32_t * group_out, int mode, uint32_t seed_state,
+                       uint64_t draw_base, float * prior_total_out) {
+    return guarded([&] {
+        Gibbs * e = g->impl.read();
+        const int F = e->F();
+        DIST_REQUIRE(values != nullptr || F == 0 || n_rows == 0,
+                     "null argument");
+        std::vector<DeviceBuf<uint32_t>> cols((size_t)F);
+        std::vector<const uint32_t *> ptrs((size_t)F);
+        for (int f = 0; f < F && n_rows; ++f) {
+            DIST_REQUIRE(values[f] != nullptr, "null value column");
+            cols[f].upload(values[f], n_rows);
+            ptrs[f] = cols[f].p;
+        }
+        DeviceBuf<float> logp;
+        DeviceBuf<uint32_t> group;
+        if (logp_out) logp.reserve(std::max<size_t>(n_rows, 1), 0);
+        if (group_out) group.reserve(std::max<size_t>(n_rows, 1), 0);
+        e->predict(n_rows, ptrs.data(), logp.p, group.p, mode, seed_state,
+                   draw_base, prior_total_out);
+        if (logp_out) logp.download(logp_out, n_rows);
+        if (group_out) group.download(group_out, n_rows);
+    });
+}
 size_t dist_gibbs_group_count(const dist_gibbs_t * g) {
     size_t n = (size_t)-1;
     (void)guarded([&] { n = (size_t)g->impl.read()->K(); });
@@ -6411,7 +6525,7 @@ int dist_gibbs_set_option(dist_gibbs_t * g, const char * name, int value) {
             "stream_scratch", "rows_scratch", "rows_scratch_lds_log",
             "rows_scratch_block", "rows_fold", "apply_stage", "program_all",
             "sample_prio", "rows_prio", "apply_overlap", "run_batches_cap",
-            "shared_totals", "score_rows_chunk"};
+            "shared_totals", "score_rows_chunk", "predict_chunk"};
         bool is_hook = false;
         for (const char * h : hooks) is_hook = is_hook || key == h;
         DIST_REQUIRE(hook == is_hook,
@@ -6487,6 +6601,10 @@ int dist_gibbs_set_option(dist_gibbs_t * g, const char * name, int value) {
             // takes (default 2^30, under the 2^32 of a 1-D grid)
             DIST_REQUIRE(value > 0, "score_rows_chunk: > 0");
             g->impl->score_rows_chunk = (size_t)value;
+        } else if (key == "predict_chunk") {
+            // the most query rows one k_predict launch takes (default 2^22)
+            DIST_REQUIRE(value > 0, "predict_chunk: > 0");
+            g->impl->predict_chunk = (size_t)value;
         } else if (key == "shared_totals") {
             // k_vs_tables folds every (value, group) cell's sampling total
             // and the tiles skip their total pass: 0 never, 1 where the

@@ -16,6 +16,7 @@ constexpr int kMaxF = DIST_MAX_FEATURES;
 // (split by path; the order matters: later parts use the earlier ones)
 #include "kernels_api.h"
 #include "kernels_rows.h"
+#include "kernels_predict.h"
 #include "kernels_vs.h"
 #include "kernels_apply.h"
 #include "kernels_hyper.h"

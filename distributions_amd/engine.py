@@ -134,6 +134,46 @@ class Gibbs(object):
     def row_scores(self, row):
         return self.core.row_scores(row)
 
+    # -- held-out rows ------------------------------------------------------
+    _PREDICT_MODES = {"sample": 0, "map": 1, None: None}
+
+    def predict(self, values, mode="sample", seed=0, draw_base=0):
+        """Rows that are NOT in the table, against the current state.
+        values: one host array per feature.  -> (logp, groups, prior_total):
+        logp[q] = log_sum_exp over all groups, empty ones included, of the
+        clustering model's score_value plus every feature's (mixture.hpp:
+        416-425, random.cc:78-92) -- under PitmanYor the log posterior
+        predictive density of row q; under LowEntropy, whose scores are not
+        normalised, subtract prior_total (log_sum_exp of the clustering
+        model's scores alone).  groups[q] is the row's group as a global id:
+        mode "sample" draws it with engine step draw_base + q + 1 of `seed`
+        (the batch's convention), "map" takes the first group of maximal
+        score, None leaves it out (groups is None).  Nothing in the engine
+        changes."""
+        return self.core.predict(list(values), self._PREDICT_MODES[mode],
+                                 _core.rng_seed(seed), draw_base)
+
+    def predict_torch(self, values, mode="sample", seed=0, draw_base=0):
+        """predict for device tensors (one 4-byte-per-row CUDA tensor per
+        feature): the results are tensors on the same device and nothing is
+        staged through the host.  -> (logp, groups, prior_total)"""
+        import torch
+        values = [v.contiguous() for v in values]
+        n = int(values[0].numel())
+        m = self._PREDICT_MODES[mode]
+        dev = values[0].device
+        logp = torch.empty(n, dtype=torch.float32, device=dev)
+        groups = (torch.empty(n, dtype=torch.int32, device=dev)
+                  if m is not None else None)
+        # (the library works on its own stream: what filled the tensors on
+        # torch's must be done)
+        torch.cuda.current_stream(dev).synchronize()
+        total = self.core.predict_dev(
+            [int(v.data_ptr()) for v in values], n, int(logp.data_ptr()),
+            int(groups.data_ptr()) if groups is not None else 0,
+            0 if m is None else m, _core.rng_seed(seed), draw_base)
+        return logp, groups, total
+
     # -- hyper-parameters ---------------------------------------------------
     # The step the reference alternates with assignment sweeps
     # (mixture.hpp:427-438, then sample_from_scores and init()), on the
@@ -433,6 +473,14 @@ class ShardedGibbs(object):
     def _whole(self):
         if self._comm is not None and getattr(self, "_partitioned", False):
             self.backend.gather_cells(self._comm)
+
+    def predict(self, values, mode="sample", seed_state=0, draw_base=0):
+        """Each rank predicts ITS queries against the common state (as
+        Gibbs.predict; seed_state is a raw engine state, as sweep's).  A
+        value-partitioned rank gathers its cells first."""
+        self._whole()
+        return self.backend.predict(list(values), Gibbs._PREDICT_MODES[mode],
+                                    seed_state, draw_base)
 
     def score_data(self):
         self._whole()

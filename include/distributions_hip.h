@@ -545,6 +545,51 @@ int dist_gibbs_row_scores(dist_gibbs_t * g, size_t row, float * scores_out,
  * launched in chunks of whole rows under the 1-D grid limit. */
 int dist_gibbs_score_rows_dev(dist_gibbs_t * g, size_t row_begin,
                               size_t row_end, float * scores_dev, size_t ld);
+/* Held-out rows: rows that are NOT in the table, scored against the current
+ * state.  For query row q with values values[f][q]:
+ *   scores[k], k in [0, dist_gibbs_group_count), empty groups included (they
+ *     carry the new-group mass): the driver's score_value (clustering.hpp:
+ *     195-208; under LowEntropy the generic MixtureDriver's, mixture.hpp:
+ *     124-141) plus every slave's score_value in feature order (mixture.hpp:
+ *     416-425) -- the arithmetic and order of dist_gibbs_score_rows_dev, with
+ *     nothing removed first: a held-out row belongs to no group;
+ *   logp[q] = log_sum_exp(scores) (random.cc:78-92): the maximum, the
+ *     in-order float sum of fast_exp(scores[k] - max), fast_log(total) + max.
+ *     Under PitmanYor the driver's scores are normalised and logp[q] is the
+ *     log posterior predictive density of the row; under LowEntropy they are
+ *     not, and *prior_total_out, log_sum_exp of the driver's scores alone, is
+ *     what the caller subtracts;
+ *   group[q]: mode 0 draws it by sample_from_scores_overwrite (random.hpp:
+ *     361-366 over random.cc:94-106 and random.hpp:316-333) with engine step
+ *     draw_base + q + 1 of seed_state, the batch's own convention, so that
+ *     results do not depend on chunking or launch geometry; mode 1 takes the
+ *     first index that attains the maximum.  Either way the GLOBAL group id,
+ *     as dist_gibbs_assignments returns them.
+ * values: F columns of n_rows 32-bit words (float bits for
+ * NormalInverseChiSq), every feature observed.  logp, group and
+ * prior_total_out may each be NULL.  A DirichletDiscrete value >= dim or a
+ * BetaBernoulli value > 1 reads nothing out of bounds: the call fails with
+ * dist_last_error() naming the first such row and its feature, and the
+ * outputs are then unspecified.  A DirichletProcessDiscrete value the table
+ * does not hold (>= its size, DIST_DPD_OTHER among them) is valid and scores
+ * as OTHER (dpd.hpp:534-542).  A pure reader: rows, statistics, id maps,
+ * caches and random state of the engine are left as they were; a run a sweep
+ * left open is closed and stays resumable.  Refused while a batch is open and
+ * on a value-partitioned rank whose cells are stale (dist_gibbs_gather_cells
+ * first).  n_rows == 0 does nothing.  Returns when the work is done.  Memory:
+ * O(n_rows + group count); no n_rows x groups matrix exists anywhere.
+ * _dev: device pointers throughout (values_dev itself is a host array of F
+ * device pointers), prior_total_out a host scalar.  The host form stages,
+ * calls and downloads. */
+int dist_gibbs_predict_dev(dist_gibbs_t * g, size_t n_rows,
+                           const uint32_t * const * values_dev,
+                           float * logp_dev, uint32_t * group_dev, int mode,
+                           uint32_t seed_state, uint64_t draw_base,
+                           float * prior_total_out);
+int dist_gibbs_predict(dist_gibbs_t * g, size_t n_rows,
+                       const uint32_t * const * values, float * logp_out,
+                       uint32_t * group_out, int mode, uint32_t seed_state,
+                       uint64_t draw_base, float * prior_total_out);
 
 size_t dist_gibbs_group_count(const dist_gibbs_t * g);     /* counts().size() */
 size_t dist_gibbs_row_count(const dist_gibbs_t * g);
@@ -679,7 +724,9 @@ int dist_gibbs_sharded_device_normalise_ok(const dist_gibbs_t * g,
  * before they do), run_batches_cap (a device-normalised run covers at most
  * this many batches: 0 as many as fit -- tests/test_gpu_native_ranks.py sees a
  * run used up and the ranks agree on the next one), score_rows_chunk (the most
- * (row, group) work-items one dist_gibbs_score_rows_dev launch takes: 2^30).
+ * (row, group) work-items one dist_gibbs_score_rows_dev launch takes: 2^30),
+ * predict_chunk (the most query rows one dist_gibbs_predict launch takes:
+ * 2^22).
  */
 int dist_gibbs_set_option(dist_gibbs_t * g, const char * name, int value);
 /* how many batches each score+sample kernel has served */
