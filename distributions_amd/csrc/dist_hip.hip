@@ -13,9 +13,11 @@
 #include <memory>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <map>
 #include <mutex>
 #include <set>
+#include <utility>
 
 #include "common.h"
 #include "comm.h"
@@ -306,6 +308,79 @@ static inline dim3 grid_for(size_t n, int block = kBlock) {
                            __VA_ARGS__);                                     \
         HIP_CHECK(hipGetLastError());                                        \
     } while (0)
+
+
+// A launch with dynamic LDS (sized by the kernel's own <kernel>_lds function,
+// kernels*.h).  Beyond kLdsNoOptIn bytes the kernel instance has to opt in:
+// the limit is raised, never lowered, when `lds` exceeds what THIS instance
+// was raised to on the current device -- lds_raised_to's static is per kernel
+// instance, so no two instances share a slot.  Smaller launches cost no HIP
+// call beside the launch itself.  A caller with several such launches asks for
+// the device once and hands it to launch_lds_on; device < 0: asked for here.
+template <auto Kernel>
+static std::atomic<size_t> * lds_raised_to() {
+    static std::atomic<size_t> by_device[64];
+    return by_device;
+}
+template <auto Kernel, class... A>
+static void launch_lds_on(int device, dim3 grid, dim3 block, size_t lds,
+                          A &&... args) {
+    if (lds > kLdsNoOptIn) {
+        if (device < 0) HIP_CHECK(hipGetDevice(&device));
+        std::atomic<size_t> & have = lds_raised_to<Kernel>()[device & 63];
+        if (lds > have.load(std::memory_order_relaxed)) {
+            HIP_CHECK(hipFuncSetAttribute(
+                reinterpret_cast<const void *>(Kernel),
+                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            have.store(lds, std::memory_order_relaxed);
+        }
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, stream(),
+                       std::forward<A>(args)...);
+    HIP_CHECK(hipGetLastError());
+}
+template <auto Kernel, class... A>
+static void launch_lds(dim3 grid, dim3 block, size_t lds, A &&... args) {
+    launch_lds_on<Kernel>(-1, grid, block, lds, std::forward<A>(args)...);
+}
+// k_chains' form: the attribute is set to this launch's size on EVERY launch
+// and its status dropped, see ChainsLaunch.
+template <auto Kernel, class... A>
+static void launch_lds_unchecked(dim3 grid, dim3 block, size_t lds,
+                                 A &&... args) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(Kernel, grid, block, lds, stream(),
+                       std::forward<A>(args)...);
+    HIP_CHECK(hipGetLastError());
+}
+
+// The single-feature kernels are instantiated per kind of the first feature:
+// fn.go<KIND>() for DD, DPD, GP and BNB; anything else takes BB's.
+template <class Fn>
+static void dispatch_kind(int kind, Fn && fn) {
+    switch (kind) {
+    case DIST_DD: fn.template go<DIST_DD>(); break;
+    case DIST_DPD: fn.template go<DIST_DPD>(); break;
+    case DIST_GP: fn.template go<DIST_GP>(); break;
+    case DIST_BNB: fn.template go<DIST_BNB>(); break;
+    default: fn.template go<DIST_BB>(); break;
+    }
+}
+
+// ... for a generic lambda: body(std::integral_constant<int, KIND>())
+template <class Body>
+struct KindCall {
+    Body & body;
+    template <int KIND>
+    void go() { body(std::integral_constant<int, KIND>()); }
+};
+template <class Body>
+static void dispatch_kind_call(int kind, Body && body) {
+    dispatch_kind(kind, KindCall<std::remove_reference_t<Body>>{body});
+}
 
 static void sync() { HIP_CHECK(hipStreamSynchronize(stream())); }
 
@@ -1064,6 +1139,14 @@ struct Tracker {
 // ---------------------------------------------------------------------------
 // Gibbs: the batched row engine
 
+// (splitmix64's finaliser: the header's signatures)
+static uint64_t mix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
 struct Gibbs {
     float alpha, d;
     int cluster = 0;        // 0 PitmanYor(alpha, d), 1 LowEntropy(dataset_size)
@@ -1384,7 +1467,7 @@ struct Gibbs {
     int device_normalise_mode = 2;
     // dist_gibbs_sweep_sharded may normalise on the device (the ranks agree
     // on it among themselves when a run is opened)
-    bool sharded_device_normalise = true;
+    int sharded_device_normalise = 1;
     uint64_t async_batches = 0;
     std::vector<hipEvent_t> ev_pool;
 
@@ -2374,27 +2457,25 @@ struct Gibbs {
         if (n_ops > 4) shape = 0;
         const void * fn = nullptr;
         int shape_id = 0;
-#define ROWS_SCRATCH_M(M, SHAPE)                                             \
-        do {                                                                 \
-            if (lds_log)                                                     \
-                fn = (const void *)&k_rows_scratch<M, true, SHAPE>;          \
-            else                                                             \
-                fn = (const void *)&k_rows_scratch<M, false, SHAPE>;         \
-        } while (0)
-#define ROWS_SCRATCH(ID, SHAPE)                                              \
-        do {                                                                 \
-            shape_id = ID;                                                   \
-            if (scan) ROWS_SCRATCH_M(true, SHAPE);                           \
-            else ROWS_SCRATCH_M(false, SHAPE);                               \
-        } while (0)
-        if (shape == kShapeGN) ROWS_SCRATCH(1, kShapeGN);
-        else if (shape == kShapeN) ROWS_SCRATCH(2, kShapeN);
-        else if (shape == kShapeNN) ROWS_SCRATCH(3, kShapeNN);
-        else if (shape == kShapeG) ROWS_SCRATCH(4, kShapeG);
-        else if (shape == kShapeC) ROWS_SCRATCH(5, kShapeC);
-        else ROWS_SCRATCH(0, 0);
-#undef ROWS_SCRATCH
-#undef ROWS_SCRATCH_M
+        auto pick = [&](int id, auto shape_c) {
+            constexpr int SHAPE = decltype(shape_c)::value;
+            shape_id = id;
+            if (scan)
+                fn = lds_log
+                         ? (const void *)&k_rows_scratch<true, true, SHAPE>
+                         : (const void *)&k_rows_scratch<true, false, SHAPE>;
+            else
+                fn = lds_log
+                         ? (const void *)&k_rows_scratch<false, true, SHAPE>
+                         : (const void *)&k_rows_scratch<false, false, SHAPE>;
+        };
+        using std::integral_constant;
+        if (shape == kShapeGN) pick(1, integral_constant<int, kShapeGN>());
+        else if (shape == kShapeN) pick(2, integral_constant<int, kShapeN>());
+        else if (shape == kShapeNN) pick(3, integral_constant<int, kShapeNN>());
+        else if (shape == kShapeG) pick(4, integral_constant<int, kShapeG>());
+        else if (shape == kShapeC) pick(5, integral_constant<int, kShapeC>());
+        else pick(0, integral_constant<int, 0>());
         int dev = 0;
         HIP_CHECK(hipGetDevice(&dev));
         // workgroups of `block` threads resident per CU, per instance
@@ -2759,7 +2840,7 @@ struct Gibbs {
                 self->launch_tables<KIND>(*P, T, *c);
             } else
                 hipLaunchKernelGGL((k_vs_prepare<KIND>), dim3(nv), dim3(kBlock),
-                                   T.PA ? (size_t)T.Kpad * 8 : 0,
+                                   vs_prepare_lds(T.Kpad, T.PA != nullptr),
                                    stream(), *P, T, self->deferred_count.p,
                                    c->n_other);
             HIP_CHECK(hipGetLastError());
@@ -2767,9 +2848,12 @@ struct Gibbs {
             // strip of LDS once its tile was done -- off k_vs_apply's path --
             // was measured: k_vs_apply 17.4 -> 14.8 us on average, k_vs_sample
             // 79 -> 86: its 64 registers spill.)
-            const VsDefer D{self->deferred.p, self->deferred_count.p,
-                            fused ? c->def_counts.p : nullptr, c->chunks.p,
-                            0};
+            VsDefer D;
+            memset(&D, 0, sizeof(D));
+            D.list = self->deferred.p;
+            D.count = self->deferred_count.p;
+            if (fused) D.chunk_counts = c->def_counts.p;
+            D.chunks = c->chunks.p;
             self->phase_mark(1);
             {
                 HOST_PROBE(10, "      mark(ev0)");
@@ -2781,22 +2865,22 @@ struct Gibbs {
             if (narrow) {
                 // (waves alone or in pairs on their SIMDs read a whole chunk
                 // ahead; more of them half a chunk, and four fit)
-                const size_t lds =
-                    2 * ((size_t)T.Kuse + 2 * kVsUnroll) * sizeof(float);
-#define VS_NARROW(HQ)                                                        \
-                hipLaunchKernelGGL(                                          \
-                    (k_vs_narrow<KIND, HQ>), dim3(c->n_narrow_tiles),        \
-                    dim3(64), lds, stream(), *P, T, c->narrow_tiles.p,       \
-                    c->n_narrow_tiles, c->sorted_rows.p, D)
+                auto launch = [&](auto hq) {
+                    hipLaunchKernelGGL(
+                        (k_vs_narrow<KIND, decltype(hq)::value>),
+                        dim3(c->n_narrow_tiles), dim3(64),
+                        vs_narrow_lds(T.Kuse), stream(), *P, T,
+                        c->narrow_tiles.p, c->n_narrow_tiles,
+                        c->sorted_rows.p, D);
+                };
                 const bool whole =
                     self->narrow_read_ahead
                         ? self->narrow_read_ahead == 8
                         : c->n_narrow_tiles <= 8u * (uint32_t)self->cu_count();
                 if (whole)
-                    VS_NARROW(8);
+                    launch(std::integral_constant<int, 8>());
                 else
-                    VS_NARROW(4);
-#undef VS_NARROW
+                    launch(std::integral_constant<int, 4>());
                 HIP_CHECK(hipGetLastError());
                 self->mark(self->ev1);
                 return;
@@ -2838,10 +2922,8 @@ struct Gibbs {
         if ((kind0 == DIST_BNB || kind0 == DIST_GP) && c.n_other) return false;
         // (k_vs_apply's LDS follows the batch's own bound on the group
         // count, not the run's: the device lays it out by the true count)
-        const size_t lds_sort =
-            ((size_t)batch_k_limit * 2 + kVsApplyBlock / 64 + 4 * kVsApplyRows
-             + 4) * 4;
-        if (lds_sort > 144 * 1024) return false;
+        if (vs_apply_sort_lds((size_t)batch_k_limit) > kLdsWorkgroupLimit)
+            return false;
         return (size_t)c.n_chunks * K() <= ((size_t)1 << 22);
     }
     // k_vs_tables for the open batch; afterwards the OUT buffers are the live
@@ -2877,24 +2959,14 @@ struct Gibbs {
         A.d = d;
         A.n_empty = py.n_empty;
         A.sample_size = py.sample_size;
-        A.offsets = VsOffsets{c.grp_off.p, c.off_epoch.p, c.off_stride};
+        A.offsets.off = c.grp_off.p;
+        A.offsets.epoch = c.off_epoch.p;
+        A.offsets.stride = c.off_stride;
         remap_log.reserve((size_t)kRemapEpochs * kRemapEntry, 0);   // zeros
         A.remap_log = remap_log.p;
         A.k_limit = T.Kuse;
-        const size_t lds = ((size_t)T.Kpad * 4 + 2) * 4;
-        int device = 0;
-        HIP_CHECK(hipGetDevice(&device));
-        static std::atomic<size_t> opted_in[64];
-        std::atomic<size_t> & have = opted_in[device & 63];
-        if (lds > 64 * 1024 && lds > have.load(std::memory_order_relaxed)) {
-            HIP_CHECK(hipFuncSetAttribute(
-                reinterpret_cast<const void *>(&k_vs_tables<KIND>),
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            have.store(lds, std::memory_order_relaxed);
-        }
-        hipLaunchKernelGGL((k_vs_tables<KIND>), dim3(T.n_values),
-                           dim3(kTablesBlock), lds, stream(), A, T);
-        HIP_CHECK(hipGetLastError());
+        launch_lds<&k_vs_tables<KIND>>(dim3(T.n_values), dim3(kTablesBlock),
+                                       vs_tables_lds(T.Kpad), A, T);
         finish_pending = false;   // (this launch normalised the group set)
         base_valid = true;
         P.feat[0] = f.view();
@@ -2966,13 +3038,7 @@ struct Gibbs {
         VsStreamLaunch L{this, &P, &c};
         {
         HOST_PROBE(7, "    launches (L.go)");
-        switch (feats[0]->sh.kind) {
-        case DIST_DD: L.go<DIST_DD>(); break;
-        case DIST_DPD: L.go<DIST_DPD>(); break;
-        case DIST_GP: L.go<DIST_GP>(); break;
-        case DIST_BNB: L.go<DIST_BNB>(); break;
-        default: L.go<DIST_BB>(); break;
-        }
+        dispatch_kind(feats[0]->sh.kind, L);
         }
         launch_deferred(P);
     }
@@ -3003,7 +3069,7 @@ struct Gibbs {
             self->mark(self->ev0);
             hipLaunchKernelGGL((k_vs_scan_prepare<KIND>), dim3(T.n_values),
                                dim3(kVsScanBlock),
-                               T.lds_scores ? (size_t)T.Kpad * 4 : 0,
+                               vs_scan_prepare_lds(T.Kpad, T.lds_scores != 0),
                                stream(), *P, T, self->deferred_count.p,
                                c->n_other);
             self->phase_mark(1);
@@ -3034,16 +3100,16 @@ struct Gibbs {
                                      hipMemcpyDeviceToDevice, stream()));
         P.sorted_rows = c.sorted_rows.p;
         P.assign_pos = c.assign_pos.p;
-        VsScanLaunch L{this, &P, &c,
-                       VsScanTables{vsLA.p, vsPA.p, vsM.p, vsmB.p, Kpad, nv,
-                                    (size_t)Kpad * 4 <= 48 * 1024 ? 1 : 0}};
-        switch (feats[0]->sh.kind) {
-        case DIST_DD: L.go<DIST_DD>(); break;
-        case DIST_DPD: L.go<DIST_DPD>(); break;
-        case DIST_GP: L.go<DIST_GP>(); break;
-        case DIST_BNB: L.go<DIST_BNB>(); break;
-        default: L.go<DIST_BB>(); break;
-        }
+        VsScanLaunch L{this, &P, &c, {}};
+        memset(&L.T, 0, sizeof(L.T));
+        L.T.C = vsLA.p;
+        L.T.coarse = vsPA.p;
+        L.T.M = vsM.p;
+        L.T.total = vsmB.p;
+        L.T.Kpad = Kpad;
+        L.T.n_values = nv;
+        L.T.lds_scores = vs_scan_scores_in_lds(Kpad) ? 1 : 0;
+        dispatch_kind(feats[0]->sh.kind, L);
         scan_batches += 1;
         phase_mark(2);
         launch_deferred(P);
@@ -3140,30 +3206,42 @@ struct Gibbs {
         }
         P.sorted_rows = c.sorted_rows.p;
         P.assign_pos = c.assign_pos.p;
-        VsLaunch L{this, &P, &c,
-                   VsTables{vsLA.p, vsLB.p, vsM.p, vsmB.p, vsArg.p, Kpad,
-                            prefix && !totals ? vsPA.p : nullptr,
-                            prefix && !totals ? vsPB.p : nullptr,
-                            bands ? vsBandMode.p : nullptr,
-                            bands ? vsBandTile.p : nullptr, c.val_start.p,
-                            nv, nullptr, c.chunk_first.p,
-                            fused ? vsOwn.p : nullptr, Kuse, band_count,
-                            fused ? 1 : 0, sample_prio_mode,
-                            totals ? vsTot.p : nullptr}, narrow, fused};
+        VsLaunch L{this, &P, &c, {}, narrow, fused};
+        VsTables & T = L.T;
+        memset(&T, 0, sizeof(T));
+        T.LA = vsLA.p;
+        T.LB = vsLB.p;
+        T.M = vsM.p;
+        T.mB = vsmB.p;
+        T.argmax = vsArg.p;
+        T.Kpad = Kpad;
+        if (prefix && !totals) {
+            T.PA = vsPA.p;
+            T.PB = vsPB.p;
+        }
+        if (bands) {
+            T.band_mode = vsBandMode.p;
+            T.band_tile = vsBandTile.p;
+        }
+        T.val_start = c.val_start.p;
+        T.n_values = nv;
+        T.chunk_first = c.chunk_first.p;
+        T.Kuse = Kuse;
+        T.band_count = band_count;
+        if (fused) {
+            T.own = vsOwn.p;
+            T.band_by_chunk = 1;
+        }
+        T.prio_mode = sample_prio_mode;
+        if (totals) T.tot = vsTot.p;
         // DIST_VS_STAMPS=<file>: per-wave phase stamps of every launch (the
         // last one stays in the file): tools/vs_stamps.py
         static const char * stamps_path = getenv("DIST_VS_STAMPS");
         if (stamps_path) {
             vsStamps.reserve(((size_t)c.n_tiles * 2 + 4096) * 6, 0);
-            L.T.stamps = vsStamps.p;
+            T.stamps = vsStamps.p;
         }
-        switch (feats[0]->sh.kind) {
-        case DIST_DD: L.go<DIST_DD>(); break;
-        case DIST_DPD: L.go<DIST_DPD>(); break;
-        case DIST_GP: L.go<DIST_GP>(); break;
-        case DIST_BNB: L.go<DIST_BNB>(); break;
-        default: L.go<DIST_BB>(); break;
-        }
+        dispatch_kind(feats[0]->sh.kind, L);
         if (stamps_path) {
             sync();
             std::vector<unsigned long long> h(((size_t)c.n_tiles * 2 + 4096) * 6);
@@ -3194,17 +3272,13 @@ struct Gibbs {
         template <int A, int B, int NF>
         void run() {
             hipLaunchKernelGGL((k_rows_wave<A, B, NF>), dim3(blocks),
-                               dim3(kBlock),
-                               (size_t)(kBlock / 64) * ((K + 63) & ~63)
-                                   * sizeof(float),
-                               stream(), *P);
+                               dim3(kBlock), rows_wave_lds(K), stream(), *P);
             HIP_CHECK(hipGetLastError());
         }
     };
     // the wave-per-row kernel keeps K floats per wave in LDS
     bool wave_rows_fit() const {
-        return (size_t)(kBlock / 64) * ((K() + 63) & ~63) * sizeof(float)
-               <= 60 * 1024;
+        return rows_wave_lds(K()) <= kLdsStripLimit;
     }
 
     void batch_sample(size_t r0, size_t r1, uint32_t seed, uint64_t draw_base) {
@@ -3332,28 +3406,16 @@ struct Gibbs {
             cs_total.reserve(grow_capacity((size_t)n_keys), 0);
             ev_vals_sorted.reserve(n_ev, 0);
             hipLaunchKernelGGL(k_cs_hist, dim3(blocks), dim3(kCsBlock),
-                               (size_t)n_keys * 4, stream(), old_dev, new_dev,
+                               cs_hist_lds(n_keys), stream(), old_dev, new_dev,
                                n_ev, n_keys, cs_hist.p);
             hipLaunchKernelGGL(k_cs_scan,
                                dim3((n_keys + kCsBlock - 1) / kCsBlock),
                                dim3(kCsBlock), 0, stream(), cs_hist.p, blocks,
                                n_keys, cs_total.p);
-            const size_t lds = (size_t)(kCsBlock / 64 + 1) * n_keys * 4;
-            int device = 0;
-            HIP_CHECK(hipGetDevice(&device));
-            static std::atomic<size_t> opted_in[64];
-            std::atomic<size_t> & have = opted_in[device & 63];
-            if (lds > 64 * 1024 && lds > have.load(std::memory_order_relaxed)) {
-                HIP_CHECK(hipFuncSetAttribute(
-                    reinterpret_cast<const void *>(&k_cs_scatter),
-                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                have.store(lds, std::memory_order_relaxed);
-            }
-            hipLaunchKernelGGL(k_cs_scatter, dim3(blocks), dim3(kCsBlock), lds,
-                               stream(), old_dev, new_dev, n_ev, n_keys,
-                               cs_hist.p, cs_total.p, cs_base.p,
-                               ev_vals_sorted.p);
-            HIP_CHECK(hipGetLastError());
+            launch_lds<&k_cs_scatter>(dim3(blocks), dim3(kCsBlock),
+                                      cs_scatter_lds(n_keys), old_dev, new_dev,
+                                      n_ev, n_keys, cs_hist.p, cs_total.p,
+                                      cs_base.p, ev_vals_sorted.p);
             hipLaunchKernelGGL(k_replay_sorted,
                                dim3((unsigned)Kn, (unsigned)R.n), dim3(64), 0,
                                stream(), R, row_begin, ev_vals_sorted.p,
@@ -3439,7 +3501,7 @@ struct Gibbs {
     }
     bool merged_floats() const {
         return float_stats_mode == 1 && any_float_stats()
-               && (size_t)merge_layout().words * 8 <= 144 * 1024;
+               && merge_float_lds(merge_layout().words) <= kLdsWorkgroupLimit;
     }
     // the open batch's float-statistic sums into merge_image (not applied)
     void merge_float_delta() {
@@ -3456,22 +3518,10 @@ struct Gibbs {
         const unsigned blocks =
             (unsigned)((n + kApplyLdsRows - 1) / kApplyLdsRows);
         merge_stage.reserve(grow_capacity((size_t)blocks * L.words), 0);
-        const size_t lds = (size_t)L.words * 8;
-        int device = 0;
-        HIP_CHECK(hipGetDevice(&device));
-        static std::atomic<size_t> opted_in[64];
-        std::atomic<size_t> & have = opted_in[device & 63];
-        if (lds > 64 * 1024 && lds > have.load(std::memory_order_relaxed)) {
-            HIP_CHECK(hipFuncSetAttribute(
-                reinterpret_cast<const void *>(&k_merge_float_moves),
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            have.store(lds, std::memory_order_relaxed);
-        }
-        hipLaunchKernelGGL(k_merge_float_moves, dim3(blocks),
-                           dim3(kApplyLdsBlock), lds, stream(), P, L,
-                           by_pos ? old_row.p : old_packed.p,
-                           by_pos ? new_row.p : new_packed.p, merge_stage.p);
-        HIP_CHECK(hipGetLastError());
+        launch_lds<&k_merge_float_moves>(
+            dim3(blocks), dim3(kApplyLdsBlock), merge_float_lds(L.words), P, L,
+            by_pos ? old_row.p : old_packed.p,
+            by_pos ? new_row.p : new_packed.p, merge_stage.p);
         hipLaunchKernelGGL(k_merge_float_reduce,
                            dim3((unsigned)((L.words + 63) / 64)), dim3(64), 0,
                            stream(), merge_stage.p, (int)blocks, L.words,
@@ -3512,17 +3562,12 @@ struct Gibbs {
         // (a fused batch: the bound its launches were sized with, see
         // fused_ok; the device's layout follows the true group count)
         const size_t k_lds = batch_fused ? (size_t)batch_k_limit : (size_t)K();
-        const size_t lds_sort =
-            (k_lds * 2 + kVsApplyBlock / 64 + 4 * kVsApplyRows + 4) * 4;
-        const size_t lds_plain = (size_t)K() * 4;
-        // a 1024-thread workgroup may take most of the CU's 160 KiB of LDS
-        const size_t lds_limit = 144 * 1024;
-        if (batch_value_sorted && lds_plain <= lds_limit) {
+        const size_t lds_sort = vs_apply_sort_lds(k_lds);
+        const size_t lds_plain = vs_apply_plain_lds((size_t)K());
+        if (batch_value_sorted && lds_plain <= kLdsWorkgroupLimit) {
             VsCache & c = vs_get(batch_begin, batch_end);
-            const bool sort = lds_sort <= lds_limit;
-            const bool bb = feats[0]->sh.kind == DIST_BB;
+            const bool sort = lds_sort <= kLdsWorkgroupLimit;
             const bool gp = feats[0]->sh.kind == DIST_GP;
-            const bool bnb = feats[0]->sh.kind == DIST_BNB;
             const dim3 grid(c.n_chunks), block(kVsApplyBlock);
             // one chunk per value and live statistics: the kernel keeps the
             // touched cache cells current and batch_finish skips the rebuild
@@ -3552,8 +3597,6 @@ struct Gibbs {
                 stage = vs_stage.p;
             }
             const int sole = c.one_chunk_per_value ? 1 : 0;
-            int apply_device = 0;
-            HIP_CHECK(hipGetDevice(&apply_device));
             unsigned long long * pairs = nullptr;
             unsigned pairs_seq = 0;
             if (stage && img.counts == py.d_counts.p && !async_active) {
@@ -3570,13 +3613,16 @@ struct Gibbs {
             int lds_told = 0;
             size_t lds_sort_used = lds_sort;
             if (batch_fused && sort && !gp && apply_overlap_mode) {
-                const size_t strip_bytes = ((k_lds + 63) & ~(size_t)63) * 4;
-                lds_sort_used = std::min(lds_limit, lds_sort + 4 * strip_bytes);
+                lds_sort_used = vs_apply_overlap_lds(k_lds);
                 lds_told = (int)lds_sort_used;
             }
-            const VsDefer D{deferred.p, deferred_count.p,
-                            batch_fused ? c.def_counts.p : nullptr,
-                            c.chunks.p, lds_told};
+            VsDefer D;
+            memset(&D, 0, sizeof(D));
+            D.list = deferred.p;
+            D.count = deferred_count.p;
+            if (batch_fused) D.chunk_counts = c.def_counts.p;
+            D.chunks = c.chunks.p;
+            D.lds_bytes = lds_told;
             static const bool trace_deferred = getenv("DIST_TRACE_DEFERRED");
             if (trace_deferred && batch_fused) {   // (diagnostic: drains)
                 std::vector<uint32_t> h(c.n_chunks);
@@ -3599,7 +3645,8 @@ struct Gibbs {
             // the sorting form of a device-normalised run leaves the groups'
             // offsets per chunk (bands without a walk, k_vs_tables); any
             // other form clears the stamps of a range that has some
-            VsOffsets O{nullptr, c.off_epoch.p, 0};
+            VsOffsets O;
+            memset(&O, 0, sizeof(O));
             if (sort && async_active && c.one_value_chunks) {
                 if (c.off_stride < K() + 2) {
                     c.off_stride = (int)grow_capacity((size_t)K() + 2);
@@ -3608,74 +3655,59 @@ struct Gibbs {
                     c.off_epoch.release();
                     c.off_epoch.reserve(std::max<size_t>(c.n_chunks, 1), 0);
                 }
-                O = VsOffsets{c.grp_off.p, c.off_epoch.p, c.off_stride};
+                O.off = c.grp_off.p;
+                O.stride = c.off_stride;
             }
-#define VS_APPLY(KIND, SORT, LDS)                                            \
-            do {                                                             \
-                /* beyond the default opt-in: raised (never lowered) once  \
-                 * per size, kernel instance and device */                   \
-                static std::atomic<size_t> opted_in[64];                     \
-                std::atomic<size_t> & have = opted_in[apply_device & 63];    \
-                if ((LDS) > 64 * 1024                                        \
-                    && (LDS) > have.load(std::memory_order_relaxed)) {       \
-                    HIP_CHECK(hipFuncSetAttribute(                           \
-                        reinterpret_cast<const void *>(                      \
-                            &k_vs_apply<KIND, SORT>),                        \
-                        hipFuncAttributeMaxDynamicSharedMemorySize,          \
-                        (int)(LDS)));                                        \
-                    have.store((LDS), std::memory_order_relaxed);            \
-                }                                                            \
-                hipLaunchKernelGGL((k_vs_apply<KIND, SORT>), grid, block,    \
-                                   LDS, stream(), P, img, c.chunks.p,        \
-                                   c.sorted_rows.p, d_p2g_ptr,               \
-                                   c.assign_pos.p, (uint32_t)vs_nvals(),     \
-                                   refresh, sole, stage, D, O);              \
-                if (stage)                                                   \
-                    hipLaunchKernelGGL((k_vs_reduce<KIND>), rgrid, rblock,   \
-                                       0, stream(), img, stage, c.chunks.p,  \
-                                       c.n_chunks, K(),                      \
-                                       (uint32_t)vs_nvals(), pairs,          \
-                                       pairs_seq,                            \
-                                       async_active ? dev_ptr() : nullptr,   \
-                                       k_limit(),                            \
-                                       batch_fused ? c.multi.p : nullptr,    \
-                                       batch_fused ? c.n_multi : 0u,         \
-                                       feats[0]->dim());                     \
-            } while (0)
+            O.epoch = c.off_epoch.p;   // (after the buffers may have moved)
+            // (the device once for the launches below, where one opts in)
+            int apply_device = -1;
+            if ((sort && lds_sort_used > kLdsNoOptIn)
+                || lds_plain > kLdsNoOptIn)
+                HIP_CHECK(hipGetDevice(&apply_device));
+            auto apply = [&](auto kind_c, auto sort_c) {
+                constexpr int KIND = decltype(kind_c)::value;
+                constexpr bool SORT = decltype(sort_c)::value;
+                launch_lds_on<&k_vs_apply<KIND, SORT>>(
+                    apply_device, grid, block, SORT ? lds_sort_used : lds_plain, P, img,
+                    c.chunks.p, c.sorted_rows.p, d_p2g_ptr, c.assign_pos.p,
+                    (uint32_t)vs_nvals(), refresh, sole, stage, D, O);
+                if (stage)
+                    hipLaunchKernelGGL((k_vs_reduce<KIND>), rgrid, rblock,
+                                       0, stream(), img, stage, c.chunks.p,
+                                       c.n_chunks, K(),
+                                       (uint32_t)vs_nvals(), pairs,
+                                       pairs_seq,
+                                       async_active ? dev_ptr() : nullptr,
+                                       k_limit(),
+                                       batch_fused ? c.multi.p : nullptr,
+                                       batch_fused ? c.n_multi : 0u,
+                                       feats[0]->dim());
+            };
             HOST_PROBE(12, "  apply launches");
             // chunks of several values first (their rows of the staging
             // matrix must be there when k_vs_reduce runs)
             if (c.mixed_chunks) {   // (categorical kinds only, see vs_get)
-                const size_t lds = lds_plain;
-                auto mixed = feats[0]->sh.kind == DIST_DPD
-                                 ? &k_vs_apply_mixed<DIST_DPD>
-                                 : &k_vs_apply_mixed<DIST_DD>;
-                static std::atomic<size_t> opted_in[2][64];
-                std::atomic<size_t> & have =
-                    opted_in[feats[0]->sh.kind == DIST_DPD][apply_device & 63];
-                if (lds > 64 * 1024
-                    && lds > have.load(std::memory_order_relaxed)) {
-                    HIP_CHECK(hipFuncSetAttribute(
-                        reinterpret_cast<const void *>(mixed),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    have.store(lds, std::memory_order_relaxed);
-                }
-                hipLaunchKernelGGL(mixed, grid, block, lds, stream(), P, img,
-                                   c.chunks.p, c.sorted_rows.p, d_p2g_ptr,
-                                   c.assign_pos.p, refresh, stage);
-                HIP_CHECK(hipGetLastError());
+                auto mixed = [&](auto kind_c) {
+                    launch_lds_on<&k_vs_apply_mixed<decltype(kind_c)::value>>(
+                        apply_device, grid, block, lds_plain, P, img, c.chunks.p,
+                        c.sorted_rows.p, d_p2g_ptr, c.assign_pos.p, refresh,
+                        stage);
+                };
+                if (feats[0]->sh.kind == DIST_DPD)
+                    mixed(std::integral_constant<int, DIST_DPD>());
+                else
+                    mixed(std::integral_constant<int, DIST_DD>());
             }
-            if (bb && sort) VS_APPLY(DIST_BB, true, lds_sort_used);
-            else if (bb) VS_APPLY(DIST_BB, false, lds_plain);
-            else if (gp && sort) VS_APPLY(DIST_GP, true, lds_sort_used);
-            else if (gp) VS_APPLY(DIST_GP, false, lds_plain);
-            else if (bnb && sort) VS_APPLY(DIST_BNB, true, lds_sort_used);
-            else if (bnb) VS_APPLY(DIST_BNB, false, lds_plain);
-            else if (sort && feats[0]->sh.kind == DIST_DPD)
-                VS_APPLY(DIST_DPD, true, lds_sort_used);   // (its rows' scorer)
-            else if (sort) VS_APPLY(DIST_DD, true, lds_sort_used);
-            else VS_APPLY(DIST_DD, false, lds_plain);
-#undef VS_APPLY
+            // (the plain form has no scorer of its own: DPD takes DD's)
+            dispatch_kind_call(feats[0]->sh.kind, [&](auto kind_c) {
+                constexpr int KIND = decltype(kind_c)::value;
+                if (sort)
+                    apply(kind_c, std::true_type());
+                else
+                    apply(std::integral_constant<
+                              int, KIND == DIST_DPD ? DIST_DD : KIND>(),
+                          std::false_type());
+            });
             HIP_CHECK(hipGetLastError());
         } else if (batch_value_sorted) {
             // group count too large for the LDS-aggregated kernel: un-sort
@@ -3706,7 +3738,8 @@ struct Gibbs {
         // the whole integer image in LDS (small categoricals): no global
         // atomics, the workgroups' images meet in a staging matrix
         const size_t all_words = stat_words();
-        if (apply_stage_mode && all_words * sizeof(int) <= 144 * 1024
+        if (apply_stage_mode
+            && apply_moves_stage_lds(all_words) <= kLdsWorkgroupLimit
             && n >= (size_t)4 * K()) {
             bool cat = false;
             for (auto & f : feats) cat = cat || is_cat(f->sh.kind);
@@ -3725,23 +3758,10 @@ struct Gibbs {
                 const unsigned blocks =
                     (unsigned)((n + kApplyLdsRows - 1) / kApplyLdsRows);
                 vs_stage.reserve(grow_capacity((size_t)blocks * L.words), 0);
-                const size_t lds_all = (size_t)L.words * sizeof(int);
-                int device = 0;
-                HIP_CHECK(hipGetDevice(&device));
-                static std::atomic<size_t> opted_in[64];
-                std::atomic<size_t> & have = opted_in[device & 63];
-                if (lds_all > 64 * 1024
-                    && lds_all > have.load(std::memory_order_relaxed)) {
-                    HIP_CHECK(hipFuncSetAttribute(
-                        reinterpret_cast<const void *>(&k_apply_moves_stage),
-                        hipFuncAttributeMaxDynamicSharedMemorySize,
-                        (int)lds_all));
-                    have.store(lds_all, std::memory_order_relaxed);
-                }
-                hipLaunchKernelGGL(k_apply_moves_stage, dim3(blocks),
-                                   dim3(kApplyLdsBlock), lds_all, stream(), P,
-                                   L, vs_stage.p, p2g, assign_out);
-                HIP_CHECK(hipGetLastError());
+                launch_lds<&k_apply_moves_stage>(
+                    dim3(blocks), dim3(kApplyLdsBlock),
+                    apply_moves_stage_lds((size_t)L.words), P, L, vs_stage.p,
+                    p2g, assign_out);
                 WordSegments seg;
                 memset(&seg, 0, sizeof(seg));
                 size_t end = 0;
@@ -3767,8 +3787,8 @@ struct Gibbs {
                 return;
             }
         }
-        const size_t lds = (size_t)(1 + 2 * F()) * K() * sizeof(int);
-        if (lds > 64 * 1024 || n < (size_t)4 * K()) {   // (too few to pay)
+        const size_t lds = apply_moves_lds(F(), K());
+        if (lds > kLdsNoOptIn || n < (size_t)4 * K()) {   // (too few to pay)
             LAUNCH(k_apply_moves, n, P, img, p2g, assign_out);
             return;
         }
@@ -3982,10 +4002,6 @@ struct Gibbs {
     }
 
     // ---- sweeps with the group set normalised on the device ---------------
-    // LDS of k_normalise: K + 2 ints and K / 2 + 1 slot pairs
-    static size_t normalise_lds(int K) {
-        return ((size_t)K + 2) * 4 + ((size_t)K / 2 + 1) * 8;
-    }
     // Every batch of the sweep takes the value-sorted path, the statistics
     // are integers, and the bound on the group count fits the kernels' LDS.
     // (measured, C2: with the runs left open across sweeps -- settle() -- the
@@ -4002,9 +4018,9 @@ struct Gibbs {
         return async_bound_fits((size_t)K() + n_batches * (size_t)py.n_empty);
     }
     static bool async_bound_fits(size_t bound) {
-        if (normalise_lds((int)bound) > 150 * 1024) return false;
+        if (normalise_lds((int)bound) > kNormaliseLdsLimit) return false;
         // k_vs_apply's plain form must fit (see apply_ints)
-        return bound * 4 <= 144 * 1024;
+        return vs_apply_plain_lds(bound) <= kLdsWorkgroupLimit;
     }
     void launch_normalise() {
         NormaliseParams N;
@@ -4017,20 +4033,8 @@ struct Gibbs {
         N.g2p = reinterpret_cast<int32_t *>(d_maps.p + maps_pcap);
         N.dev = dev_ptr();
         N.n_empty = py.n_empty;
-        const size_t lds = normalise_lds(K());
-        int device = 0;
-        HIP_CHECK(hipGetDevice(&device));
-        static std::atomic<size_t> opted_in[64];
-        std::atomic<size_t> & have = opted_in[device & 63];
-        if (lds > 64 * 1024 && lds > have.load(std::memory_order_relaxed)) {
-            HIP_CHECK(hipFuncSetAttribute(
-                reinterpret_cast<const void *>(&k_normalise),
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            have.store(lds, std::memory_order_relaxed);
-        }
-        hipLaunchKernelGGL(k_normalise, dim3(1), dim3(kNormaliseBlock), lds,
-                           stream(), N);
-        HIP_CHECK(hipGetLastError());
+        launch_lds<&k_normalise>(dim3(1), dim3(kNormaliseBlock),
+                                 normalise_lds(K()), N);
     }
     // batch_finish with the group set normalised by the device
     void batch_finish_device() {
@@ -4479,9 +4483,8 @@ struct Gibbs {
             if (r1 > r0 && !use_value_sorted(r1 - r0)) return false;
             if (r1 - r0 < batch) break;   // (the rest are empty)
         }
-        const size_t bound = (size_t)K() + n_batches * (size_t)py.n_empty;
-        if (normalise_lds((int)bound) > 150 * 1024) return false;
-        return bound * 4 <= 144 * 1024;
+        return async_bound_fits((size_t)K()
+                                + n_batches * (size_t)py.n_empty);
     }
 
     void sweep(size_t r0, size_t r1, size_t batch, uint32_t seed,
@@ -4535,7 +4538,7 @@ struct Gibbs {
         int init = 0;   // 1 / 2: the initialisation loops (k_chain_rows)
         template <int A, int B, int NF>
         void run() {
-            const size_t lds = (size_t)((K + 63) & ~63) * sizeof(float);
+            const size_t lds = chain_rows_lds(K);
             if (init == 1)
                 hipLaunchKernelGGL((k_chain_rows<A, B, NF, 1>), dim3(1),
                                    dim3(kBlock), lds, stream(), *P, base,
@@ -4567,10 +4570,11 @@ struct Gibbs {
     static constexpr int kChainRoom = 256;   // groups a launch may found
     static constexpr uint32_t kChainIds = 4096;   // ... and ids it may issue
     bool chain_fits() const {
-        return sequential_mode == 2 && (size_t)K() + kChainRoom <= 8192;
+        return sequential_mode == 2
+               && chains_lds(K() + kChainRoom) <= kLdsNoOptIn;
     }
     size_t chain_lds_bytes() const {
-        return (size_t)((K() + kChainRoom + 63) & ~63) * 8;
+        return chains_lds(K() + kChainRoom);
     }
     // everything the launch may grow into is reserved, the state the kernel
     // reads is put on the device
@@ -4705,13 +4709,14 @@ struct Gibbs {
         size_t lds;
         template <int A, int B, int NF, bool LOGL>
         void go() {
-            (void)hipFuncSetAttribute(
-                reinterpret_cast<const void *>(&k_chains<A, B, NF, LOGL>),
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipGetLastError();
-            hipLaunchKernelGGL((k_chains<A, B, NF, LOGL>), dim3(chains),
-                               dim3(kBlock), lds, stream(), args);
-            HIP_CHECK(hipGetLastError());
+            // Unlike the other sites: the dynamic part never passes
+            // kLdsNoOptIn (chain_fits), but the LOGL instance holds FastLog's
+            // 64 KiB table in static LDS beside it, so the instance states
+            // its need at any size, on every launch; a runtime that refuses
+            // the attribute may still launch, and a launch that cannot is
+            // reported by the launch's own check.
+            launch_lds_unchecked<&k_chains<A, B, NF, LOGL>>(
+                dim3(chains), dim3(kBlock), lds, args);
         }
         template <int A, int B, int NF>
         void run() {
@@ -4752,7 +4757,7 @@ struct Gibbs {
                 r += res.rows_done;
                 continue;
             }
-            if ((size_t)((K() + 63) & ~63) * sizeof(float) > 60 * 1024
+            if (chain_rows_lds(K()) > kLdsStripLimit
                 || sequential_mode == 0) {   // scores do not fit one LDS strip
                 sequential_row_as_batch(r, rng_state);
                 r += 1;
@@ -4797,8 +4802,7 @@ struct Gibbs {
                      "first unassigned one");
         size_t r = r0;
         while (r < r1) {
-            DIST_REQUIRE((size_t)((K() + 63) & ~63) * sizeof(float)
-                             <= 60 * 1024,
+            DIST_REQUIRE(chain_rows_lds(K()) <= kLdsStripLimit,
                          "init_sequential: too many groups for the chain "
                          "kernel's strip of LDS");
             upload_maps();
@@ -4845,7 +4849,7 @@ struct Gibbs {
     }
     // k_score_rows takes one work-item per (row, group): a launch covers at
     // most this many (debug.score_rows_chunk lowers it), whole rows each
-    size_t score_rows_chunk = (size_t)1 << 30;
+    int score_rows_chunk = 1 << 30;
     void score_rows(size_t r0, size_t r1, float * out_dev, size_t ld) {
         DIST_REQUIRE(r0 <= r1 && r1 <= n_rows && ld >= (size_t)K(),
                      "bad row range or leading dimension");
@@ -4858,7 +4862,7 @@ struct Gibbs {
         SweepParams P = params(r0, r1, 0, 0);
         prepare(P);
         const size_t step =
-            std::max<size_t>(1, score_rows_chunk / (size_t)K());
+            std::max<size_t>(1, (size_t)score_rows_chunk / (size_t)K());
         for (size_t c0 = r0; c0 < r1; c0 += step) {
             const size_t c1 = std::min(r1, c0 + step);
             P.row_begin = c0;
@@ -4870,7 +4874,7 @@ struct Gibbs {
 
     // Held-out rows (kernels_predict.h): one lane per query row, launched in
     // chunks of at most this many whole rows (debug.predict_chunk lowers it)
-    size_t predict_chunk = (size_t)1 << 22;
+    int predict_chunk = 1 << 22;
     DeviceBuf<float> predict_prior;
     DeviceBuf<SampleOut> predict_total;
     DeviceBuf<unsigned long long> predict_bad;
@@ -4898,7 +4902,7 @@ struct Gibbs {
         for (int f = 0; f < F(); ++f)
             DIST_REQUIRE(values_dev[f] != nullptr, "null value column");
         upload_maps();
-        const size_t step = std::min(n, predict_chunk);
+        const size_t step = std::min(n, (size_t)predict_chunk);
         ensure_pow_tables(step);
         SweepParams P = params(0, 0, seed_state, draw_base);
         prepare_base(P);
@@ -4941,6 +4945,268 @@ struct Gibbs {
                          + std::to_string(bad >> 8) + ", feature "
                          + std::to_string(bad & 0xFF));
     }
+
+    // ---- the ranks' loop (dist_gibbs_sweep_sharded; the caller comes in by
+    // GibbsRef::open(): a run the last pass left open may go on) ------------
+    void sweep_sharded(dist_comm_t * c, size_t n_batches, size_t batch_rows,
+                       uint32_t seed_state, uint64_t draw_base) {
+        DIST_REQUIRE(batch_rows > 0, "batch_rows must be positive");
+        DIST_REQUIRE(!any_float_stats() || merged_floats(),
+                     "order-dependent statistics are exchanged as rows "
+                     "(dist_gibbs_batch_moves_dev / replay_ordered_dev), or "
+                     "as sums with float_stats = 1");
+        // The group set is normalised on the device -- no host round trip per
+        // sub-sweep on any rank -- when EVERY rank can (one all-reduce of a
+        // flag when a run is opened: the layout of the delta image depends
+        // on it).  Like the single-engine sweep, the run then stays open
+        // across passes of the same tiling; any other call settles it.
+        Gibbs * open = this;
+        open->check_comm_fault();
+        auto agree = [&](Gibbs & e, int mine) {
+            e.agree_flag.reserve(1, 0);
+            HIP_CHECK(hipMemcpyAsync(e.agree_flag.p, &mine, sizeof(int),
+                                     hipMemcpyHostToDevice, stream()));
+            c->all_reduce(e.agree_flag.p, 1, COMM_I32, COMM_MIN, stream());
+            e.agree_flag.download(&mine, 1);
+            return mine != 0;
+        };
+        // Does the ranks' run go on?  Decided by every rank for itself, from
+        // what is the same on all of them: the tiling of this call and of the
+        // run, and the batches the run has left.  A rank that kept its run
+        // open goes on with it; a rank that closed it between the passes by
+        // LOOKING at its state (the entry points that read: GibbsRef::read)
+        // takes it up again with the same bound, the same batches left and
+        // the same origin (resume_bound): its collectives are the ones its
+        // peers issue.  No word between the ranks, no host round trip at the
+        // start of a pass (round 4 agreed on every call: 50 us per pass,
+        // profiles/r5_collective_pass.txt).  Only when the run is used up, on
+        // every rank at the same call, do they agree on a new one.  A rank
+        // that CHANGED something in between (any other entry point: options,
+        // rows, statistics, a sweep of its own) has forgotten the run and asks
+        // for a new one here while its peers go on: a caller's error, told by
+        // the host transport at once (collectives of different sizes) and,
+        // where the sizes happen to agree, by the exchange's header.
+        const bool tiling_same = open->sharded_batches == n_batches
+                                 && open->sharded_batch_rows == batch_rows;
+        bool on_device = false;
+        if (open->async_active && !open->batch_open && tiling_same
+            && n_batches <= open->async_left) {
+            on_device = true;
+        } else if (!open->async_active && !open->batch_open && tiling_same
+                   && open->resume_bound && n_batches <= open->resume_left
+                   && (size_t)open->K() + open->resume_left
+                              * (size_t)open->py.n_empty <= open->resume_bound
+                   && open->sharded_device_normalise
+                   && open->async_eligible_sharded(n_batches, batch_rows)) {
+            const size_t bound = open->resume_bound, left = open->resume_left;
+            open->async_begin(n_batches, true, bound, left);
+            open->resumed_runs += 1;
+            on_device = true;
+        }
+        if (!on_device) {
+            settle();   // (closes an open run and forgets it: GibbsRef's ->)
+            forget_resume();
+            Gibbs & s = *this;
+            on_device = agree(
+                s, s.sharded_device_normalise
+                       && s.async_eligible_sharded(n_batches, batch_rows)
+                   ? 1 : 0);
+            s.sharded_run_serial += 1;
+            if (on_device) {
+                // (the run's bound on the group count sizes the buffers: the
+                // same on every rank, so not a function of what this rank's
+                // ranges look like)
+                s.async_begin(n_batches);
+                s.sharded_batches = n_batches;
+                s.sharded_batch_rows = batch_rows;
+            } else {
+                s.sharded_batches = s.sharded_batch_rows = 0;
+            }
+        }
+        Gibbs & e = *open;
+        if (on_device) {
+            e.async_left -= std::min(e.async_left, n_batches);
+            e.async_peek_collect();
+        }
+        if (!e.comm_fault) {
+            HIP_CHECK(hipHostMalloc((void **)&e.comm_fault, sizeof(unsigned),
+                                    hipHostMallocDefault));
+            *e.comm_fault = 0;
+        }
+        const int ne = e.py.n_empty;
+        // where this rank believes the ranks' run stands at batch `done` of
+        // it, exchanging `kx` groups: two 12-bit signatures
+        auto signature = [&](size_t done, size_t kx, uint64_t & tag) {
+            uint64_t h = mix64(e.sharded_run_serial);
+            h = mix64(h ^ (uint64_t)done);
+            h = mix64(h ^ (uint64_t)kx);
+            h = mix64(h ^ (uint64_t)n_batches);
+            h = mix64(h ^ (uint64_t)batch_rows);
+            h = mix64(h ^ (uint64_t)(e.value_partitioned ? 1 : 0));
+            h = mix64(h ^ (uint64_t)(on_device ? 1 : 0));
+            tag = h | 1ull;
+            return std::make_pair((int32_t)(h & 0xFFF),
+                                  (int32_t)((h >> 12) & 0xFFF));
+        };
+        try {
+            for (size_t b = 0; b < n_batches; ++b) {
+                const size_t r0 = std::min(e.n_rows, b * batch_rows);
+                const size_t r1 = std::min(e.n_rows, r0 + batch_rows);
+                // the groups this batch's deltas can touch: rank-independent
+                // (the run's bound only sizes buffers, see exchange_K)
+                const size_t kx = e.exchange_K();
+                const size_t done = on_device ? e.run_origin_done : b;
+                if (on_device) e.async_sample(r0, r1, seed_state, draw_base);
+                else e.batch_sample(r0, r1, seed_state, draw_base);
+                const size_t words = e.exchange_words(kx);
+                const size_t total = kCommHeaderWords + words;
+                // the exchange buffer is zeroed once; k_add_words clears what
+                // it consumes, so it is all zero again before every batch
+                if (total > e.delta_image.cap || !e.delta_image.p) {
+                    e.delta_image.reserve(grow_capacity(total), 0);
+                    HIP_CHECK(hipMemsetAsync(e.delta_image.p, 0,
+                                             e.delta_image.cap * 4, stream()));
+                    e.delta_header_tag = 0;
+                }
+                int32_t * image = e.delta_image.p + kCommHeaderWords;
+                uint64_t tag = 0;
+                const auto sig = signature(done, kx, tag);
+                if (e.delta_header_tag != tag)   // (not left by the last batch)
+                    hipLaunchKernelGGL(k_comm_header, dim3(1), dim3(1), 0,
+                                       stream(), e.delta_image.p, sig.first,
+                                       sig.second);
+                e.batch_delta_exchange(image, kx);
+                // in place, on the engine's stream: no hop to another stream
+                const bool timed = e.kernel_timing > 0
+                                   && e.comm_tick++ % (uint64_t)e.kernel_timing
+                                          == 0;
+                hipEvent_t t0 = nullptr, t1 = nullptr;
+                if (timed) {
+                    t0 = e.comm_event();
+                    t1 = e.comm_event();
+                    HIP_CHECK(hipEventRecord(t0, stream()));
+                }
+                c->all_reduce(e.delta_image.p, total, COMM_I32, COMM_SUM,
+                              stream());
+                e.comm_collectives += 1;
+                e.comm_words_total += total;
+                e.comm_words_last = total;
+                e.comm_words_max = std::max<uint64_t>(e.comm_words_max, total);
+                if (timed) {
+                    HIP_CHECK(hipEventRecord(t1, stream()));
+                    e.comm_ev_pending.emplace_back(t0, t1);
+                }
+                // the kernel that consumes the sum checks the header and
+                // leaves the NEXT batch's behind (no launch of its own then)
+                CommCheck chk;
+                memset(&chk, 0, sizeof(chk));
+                chk.header = e.delta_image.p;
+                chk.world = c->world;
+                chk.fault = e.comm_fault;
+                chk.tag = (unsigned)(e.comm_collectives & 0x7FFFFFFFu)
+                          | 0x80000000u;
+                e.delta_header_tag = 0;
+                if (b + 1 < n_batches) {
+                    const size_t kx_next =
+                        on_device ? std::min<size_t>(
+                                        (size_t)e.K(),
+                                        e.run_origin_K0
+                                            + (e.run_origin_done + 1) * (size_t)ne)
+                                  : 0;
+                    if (on_device) {
+                        uint64_t tag_next = 0;
+                        const auto nx = signature(done + 1, kx_next, tag_next);
+                        chk.next[0] = nx.first;
+                        chk.next[1] = nx.first * nx.first;
+                        chk.next[2] = nx.second;
+                        chk.next[3] = nx.second * nx.second;
+                        e.delta_header_tag = tag_next;
+                    }
+                }
+                e.batch_apply_words(image, true, kx, !e.value_partitioned, chk);
+                if (on_device) e.run_origin_done += 1;
+                if (e.merged_floats()) {   // the float statistics as sums
+                    e.merge_float_delta();
+                    c->all_reduce(e.merge_image.p,
+                                  (size_t)e.merge_layout().words, COMM_F64,
+                                  COMM_SUM, stream());
+                    e.merge_float_apply(e.merge_image.p);
+                }
+                if (on_device) e.batch_finish_device();
+                else e.batch_finish();
+            }
+            if (on_device) e.async_peek();
+        } catch (...) {
+            if (on_device) e.async_end(true);
+            throw;
+        }
+        if (!on_device) {
+            dist::sync();
+            e.collect_comm_timing();
+            e.check_comm_fault();
+        }
+        // (an on-device run stays open: Gibbs::settle)
+    }
+
+    // ---- value-partitioned ranks ------------------------------------------
+    void partition_by_value(dist_comm_t * c) {
+        Gibbs & e = *this;
+        DIST_REQUIRE(e.F() == 1 && is_cat(e.feats[0]->sh.kind)
+                         && e.feats[0]->dim() > 0,
+                     "value partitioning takes engines with one categorical "
+                     "feature (DirichletDiscrete, DirichletProcessDiscrete)");
+        DIST_REQUIRE(!e.batch_open, "a batch is open");
+        const int dim = e.feats[0]->dim();
+        DeviceBuf<int32_t> has;
+        has.reserve((size_t)dim * 2, 0);   // [mine | everybody's]
+        if (e.n_rows)
+            LAUNCH(k_value_presence,
+                   std::min<size_t>(e.n_rows, (size_t)2048 * kBlock),
+                   e.values[0], e.n_rows, dim, has.p);
+        HIP_CHECK(hipMemcpyAsync(has.p + dim, has.p, (size_t)dim * 4,
+                                 hipMemcpyDeviceToDevice, stream()));
+        c->all_reduce(has.p + dim, (size_t)dim, COMM_I32, COMM_SUM, stream());
+        std::vector<int32_t> h((size_t)dim * 2);
+        has.download(h.data(), h.size());
+        std::vector<int32_t> owned((size_t)dim);
+        e.present_values = 0;
+        for (int x = 0; x < dim; ++x) {
+            e.present_values += h[x] ? 1 : 0;
+            DIST_REQUIRE(h[(size_t)dim + x] <= 1,
+                         "value " + std::to_string(x) + " has rows on "
+                         + std::to_string(h[(size_t)dim + x])
+                         + " ranks: not a partition by value");
+            // (a value nobody has rows of: its cells never change; rank 0's)
+            owned[x] = h[x] || (h[(size_t)dim + x] == 0 && c->rank == 0);
+        }
+        e.owned_values.upload(owned.data(), owned.size());
+        e.value_partitioned = true;
+        dist::sync();
+    }
+    void gather_cells(dist_comm_t * c) {
+        Gibbs & e = *this;
+        DIST_REQUIRE(e.value_partitioned, "not a value-partitioned engine");
+        DIST_REQUIRE(!e.batch_open, "a batch is open");
+        const int dim = e.feats[0]->dim();
+        const size_t cells = (size_t)e.K() * dim;
+        DeviceBuf<int32_t> image;
+        image.reserve(std::max<size_t>(cells, 1), 0);
+        if (cells)
+            LAUNCH(k_owned_cells, cells, e.feats[0]->cnt.p, e.owned_values.p,
+                   cells, dim, image.p);
+        c->all_reduce(image.p, cells, COMM_I32, COMM_SUM, stream());
+        if (cells)
+            HIP_CHECK(hipMemcpyAsync(e.feats[0]->cnt.p, image.p, cells * 4,
+                                     hipMemcpyDeviceToDevice, stream()));
+        e.cells_partial = false;
+        e.rebuild_caches();
+        dist::sync();
+    }
+    // M engines' exact chains in launches of their own (defined behind
+    // GibbsRef, whose -> settles each engine)
+    static void sweep_sequential_many(dist_gibbs_t * const * engines, size_t m,
+                                      size_t row_begin, size_t row_end,
+                                      uint32_t * rng_states);
 };
 
 }  // namespace dist
@@ -4985,6 +5251,86 @@ struct GibbsRef {
     void reset(Gibbs * q) { p.reset(q); }
 };
 struct dist_gibbs { GibbsRef impl; };
+
+void dist::Gibbs::sweep_sequential_many(dist_gibbs_t * const * engines,
+                                        size_t m, size_t row_begin,
+                                        size_t row_end, uint32_t * rng_states) {
+    DIST_REQUIRE(m == 0 || (engines && rng_states), "null argument");
+    if (!m) return;
+    std::vector<Gibbs *> e(m);
+    for (size_t i = 0; i < m; ++i) {
+        DIST_REQUIRE(engines[i], "null engine");
+        e[i] = &*engines[i]->impl;   // (settles, forgets a sharded run)
+        for (size_t j = 0; j < i; ++j)
+            DIST_REQUIRE(e[j] != e[i], "the same engine twice");
+        DIST_REQUIRE(e[i]->F() == e[0]->F(), "engines of one feature list");
+        for (int f = 0; f < e[0]->F(); ++f)
+            DIST_REQUIRE(e[i]->feats[f]->sh.kind == e[0]->feats[f]->sh.kind,
+                         "engines of one feature list");
+    }
+    // chains whose group count is beyond the kernel's strips (or with the
+    // kernel switched off) take their own path, one after the other
+    std::vector<size_t> at(m, row_begin);
+    std::vector<size_t> todo;
+    for (size_t i = 0; i < m; ++i) {
+        if (e[i]->chain_fits()) {
+            todo.push_back(i);
+        } else {
+            e[i]->sweep_sequential(row_begin, row_end, &rng_states[i]);
+            at[i] = row_end;
+        }
+    }
+    std::vector<ChainArgs> args;
+    while (!todo.empty()) {
+        args.clear();
+        size_t lds = 0;
+        for (size_t i : todo) {
+            args.push_back(e[i]->chain_prepare(at[i], row_end,
+                                               rng_states[i]));
+            lds = std::max(lds, e[i]->chain_lds_bytes());
+        }
+        Gibbs & first = *e[todo[0]];
+        first.chain_args.upload(args.data(), args.size());
+        ChainsLaunch L{first.chain_args.p, (unsigned)todo.size(), lds};
+        first.dispatch(L);
+        first.chain_launches += 1;
+        // every engine's small downloads queued, then ONE wait
+        std::vector<size_t> slot_at(todo.size());
+        size_t slots = 0;
+        for (size_t j = 0; j < todo.size(); ++j) {
+            slot_at[j] = slots;
+            slots += (e[todo[j]]->chain_slot_bytes() + 63) & ~(size_t)63;
+        }
+        char * pinned = chain_pinned(std::max<size_t>(slots, 64));
+        for (size_t j = 0; j < todo.size(); ++j)
+            e[todo[j]]->chain_collect_enqueue(
+                pinned + slot_at[j],
+                e[todo[j]]->K() + kChainRoom);
+        HIP_CHECK(hipStreamSynchronize(stream()));
+        std::vector<size_t> again;
+        for (size_t j = 0; j < todo.size(); ++j) {
+            const size_t i = todo[j];
+            const ChainResult res =
+                e[i]->chain_collect_finish(pinned + slot_at[j]);
+            DIST_REQUIRE(res.rows_done > 0 || res.event != 3
+                             || at[i] >= row_end,
+                         "internal: the chain kernel found no room");
+            rng_states[i] = res.rng_state;
+            at[i] += res.rows_done;
+            // (out of room, or a group count beyond the strips now)
+            if (at[i] < row_end) {
+                if (e[i]->chain_fits()) {
+                    again.push_back(i);
+                } else {
+                    e[i]->sweep_sequential(at[i], row_end, &rng_states[i]);
+                    at[i] = row_end;
+                }
+            }
+        }
+        todo.swap(again);
+    }
+    dist::sync();
+}
 
 extern "C" {
 
@@ -5844,213 +6190,14 @@ int dist_comm_all_reduce_dev(dist_comm_t * c, void * data_dev, size_t count,
         HIP_CHECK(hipStreamSynchronize(stream()));
     });
 }
-// (splitmix64's finaliser: the header's signatures)
-static uint64_t mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
+
 int dist_gibbs_sweep_sharded(dist_gibbs_t * g, dist_comm_t * c,
                              size_t n_batches, size_t batch_rows,
                              uint32_t seed_state, uint64_t draw_base) {
     return guarded([&] {
         DIST_REQUIRE(c && c->valid(), "no communicator");
-        DIST_REQUIRE(batch_rows > 0, "batch_rows must be positive");
-        DIST_REQUIRE(!g->impl.open()->any_float_stats()
-                         || g->impl.open()->merged_floats(),
-                     "order-dependent statistics are exchanged as rows "
-                     "(dist_gibbs_batch_moves_dev / replay_ordered_dev), or "
-                     "as sums with float_stats = 1");
-        // The group set is normalised on the device -- no host round trip per
-        // sub-sweep on any rank -- when EVERY rank can (one all-reduce of a
-        // flag when a run is opened: the layout of the delta image depends
-        // on it).  Like the single-engine sweep, the run then stays open
-        // across passes of the same tiling; any other call settles it.
-        Gibbs * open = g->impl.open();
-        open->check_comm_fault();
-        auto agree = [&](Gibbs & e, int mine) {
-            e.agree_flag.reserve(1, 0);
-            HIP_CHECK(hipMemcpyAsync(e.agree_flag.p, &mine, sizeof(int),
-                                     hipMemcpyHostToDevice, stream()));
-            c->all_reduce(e.agree_flag.p, 1, COMM_I32, COMM_MIN, stream());
-            e.agree_flag.download(&mine, 1);
-            return mine != 0;
-        };
-        // Does the ranks' run go on?  Decided by every rank for itself, from
-        // what is the same on all of them: the tiling of this call and of the
-        // run, and the batches the run has left.  A rank that kept its run
-        // open goes on with it; a rank that closed it between the passes by
-        // LOOKING at its state (the entry points that read: GibbsRef::read)
-        // takes it up again with the same bound, the same batches left and
-        // the same origin (resume_bound): its collectives are the ones its
-        // peers issue.  No word between the ranks, no host round trip at the
-        // start of a pass (round 4 agreed on every call: 50 us per pass,
-        // profiles/r5_collective_pass.txt).  Only when the run is used up, on
-        // every rank at the same call, do they agree on a new one.  A rank
-        // that CHANGED something in between (any other entry point: options,
-        // rows, statistics, a sweep of its own) has forgotten the run and asks
-        // for a new one here while its peers go on: a caller's error, told by
-        // the host transport at once (collectives of different sizes) and,
-        // where the sizes happen to agree, by the exchange's header.
-        const bool tiling_same = open->sharded_batches == n_batches
-                                 && open->sharded_batch_rows == batch_rows;
-        bool on_device = false;
-        if (open->async_active && !open->batch_open && tiling_same
-            && n_batches <= open->async_left) {
-            on_device = true;
-        } else if (!open->async_active && !open->batch_open && tiling_same
-                   && open->resume_bound && n_batches <= open->resume_left
-                   && (size_t)open->K() + open->resume_left
-                              * (size_t)open->py.n_empty <= open->resume_bound
-                   && open->sharded_device_normalise
-                   && open->async_eligible_sharded(n_batches, batch_rows)) {
-            const size_t bound = open->resume_bound, left = open->resume_left;
-            open->async_begin(n_batches, true, bound, left);
-            open->resumed_runs += 1;
-            on_device = true;
-        }
-        if (!on_device) {
-            Gibbs & s = *g->impl;   // (settles an open run, forgets it)
-            on_device = agree(
-                s, s.sharded_device_normalise
-                       && s.async_eligible_sharded(n_batches, batch_rows)
-                   ? 1 : 0);
-            s.sharded_run_serial += 1;
-            if (on_device) {
-                // (the run's bound on the group count sizes the buffers: the
-                // same on every rank, so not a function of what this rank's
-                // ranges look like)
-                s.async_begin(n_batches);
-                s.sharded_batches = n_batches;
-                s.sharded_batch_rows = batch_rows;
-            } else {
-                s.sharded_batches = s.sharded_batch_rows = 0;
-            }
-        }
-        Gibbs & e = *open;
-        if (on_device) {
-            e.async_left -= std::min(e.async_left, n_batches);
-            e.async_peek_collect();
-        }
-        if (!e.comm_fault) {
-            HIP_CHECK(hipHostMalloc((void **)&e.comm_fault, sizeof(unsigned),
-                                    hipHostMallocDefault));
-            *e.comm_fault = 0;
-        }
-        const int ne = e.py.n_empty;
-        // where this rank believes the ranks' run stands at batch `done` of
-        // it, exchanging `kx` groups: two 12-bit signatures
-        auto signature = [&](size_t done, size_t kx, uint64_t & tag) {
-            uint64_t h = mix64(e.sharded_run_serial);
-            h = mix64(h ^ (uint64_t)done);
-            h = mix64(h ^ (uint64_t)kx);
-            h = mix64(h ^ (uint64_t)n_batches);
-            h = mix64(h ^ (uint64_t)batch_rows);
-            h = mix64(h ^ (uint64_t)(e.value_partitioned ? 1 : 0));
-            h = mix64(h ^ (uint64_t)(on_device ? 1 : 0));
-            tag = h | 1ull;
-            return std::make_pair((int32_t)(h & 0xFFF),
-                                  (int32_t)((h >> 12) & 0xFFF));
-        };
-        try {
-            for (size_t b = 0; b < n_batches; ++b) {
-                const size_t r0 = std::min(e.n_rows, b * batch_rows);
-                const size_t r1 = std::min(e.n_rows, r0 + batch_rows);
-                // the groups this batch's deltas can touch: rank-independent
-                // (the run's bound only sizes buffers, see exchange_K)
-                const size_t kx = e.exchange_K();
-                const size_t done = on_device ? e.run_origin_done : b;
-                if (on_device) e.async_sample(r0, r1, seed_state, draw_base);
-                else e.batch_sample(r0, r1, seed_state, draw_base);
-                const size_t words = e.exchange_words(kx);
-                const size_t total = kCommHeaderWords + words;
-                // the exchange buffer is zeroed once; k_add_words clears what
-                // it consumes, so it is all zero again before every batch
-                if (total > e.delta_image.cap || !e.delta_image.p) {
-                    e.delta_image.reserve(grow_capacity(total), 0);
-                    HIP_CHECK(hipMemsetAsync(e.delta_image.p, 0,
-                                             e.delta_image.cap * 4, stream()));
-                    e.delta_header_tag = 0;
-                }
-                int32_t * image = e.delta_image.p + kCommHeaderWords;
-                uint64_t tag = 0;
-                const auto sig = signature(done, kx, tag);
-                if (e.delta_header_tag != tag)   // (not left by the last batch)
-                    hipLaunchKernelGGL(k_comm_header, dim3(1), dim3(1), 0,
-                                       stream(), e.delta_image.p, sig.first,
-                                       sig.second);
-                e.batch_delta_exchange(image, kx);
-                // in place, on the engine's stream: no hop to another stream
-                const bool timed = e.kernel_timing > 0
-                                   && e.comm_tick++ % (uint64_t)e.kernel_timing
-                                          == 0;
-                hipEvent_t t0 = nullptr, t1 = nullptr;
-                if (timed) {
-                    t0 = e.comm_event();
-                    t1 = e.comm_event();
-                    HIP_CHECK(hipEventRecord(t0, stream()));
-                }
-                c->all_reduce(e.delta_image.p, total, COMM_I32, COMM_SUM,
-                              stream());
-                e.comm_collectives += 1;
-                e.comm_words_total += total;
-                e.comm_words_last = total;
-                e.comm_words_max = std::max<uint64_t>(e.comm_words_max, total);
-                if (timed) {
-                    HIP_CHECK(hipEventRecord(t1, stream()));
-                    e.comm_ev_pending.emplace_back(t0, t1);
-                }
-                // the kernel that consumes the sum checks the header and
-                // leaves the NEXT batch's behind (no launch of its own then)
-                CommCheck chk;
-                memset(&chk, 0, sizeof(chk));
-                chk.header = e.delta_image.p;
-                chk.world = c->world;
-                chk.fault = e.comm_fault;
-                chk.tag = (unsigned)(e.comm_collectives & 0x7FFFFFFFu)
-                          | 0x80000000u;
-                e.delta_header_tag = 0;
-                if (b + 1 < n_batches) {
-                    const size_t kx_next =
-                        on_device ? std::min<size_t>(
-                                        (size_t)e.K(),
-                                        e.run_origin_K0
-                                            + (e.run_origin_done + 1) * (size_t)ne)
-                                  : 0;
-                    if (on_device) {
-                        uint64_t tag_next = 0;
-                        const auto nx = signature(done + 1, kx_next, tag_next);
-                        chk.next[0] = nx.first;
-                        chk.next[1] = nx.first * nx.first;
-                        chk.next[2] = nx.second;
-                        chk.next[3] = nx.second * nx.second;
-                        e.delta_header_tag = tag_next;
-                    }
-                }
-                e.batch_apply_words(image, true, kx, !e.value_partitioned, chk);
-                if (on_device) e.run_origin_done += 1;
-                if (e.merged_floats()) {   // the float statistics as sums
-                    e.merge_float_delta();
-                    c->all_reduce(e.merge_image.p,
-                                  (size_t)e.merge_layout().words, COMM_F64,
-                                  COMM_SUM, stream());
-                    e.merge_float_apply(e.merge_image.p);
-                }
-                if (on_device) e.batch_finish_device();
-                else e.batch_finish();
-            }
-            if (on_device) e.async_peek();
-        } catch (...) {
-            if (on_device) e.async_end(true);
-            throw;
-        }
-        if (!on_device) {
-            dist::sync();
-            e.collect_comm_timing();
-            e.check_comm_fault();
-        }
-        // (an on-device run stays open: Gibbs::settle)
+        g->impl.open()->sweep_sharded(c, n_batches, batch_rows, seed_state,
+                                      draw_base);
     });
 }
 
@@ -6058,60 +6205,13 @@ int dist_gibbs_sweep_sharded(dist_gibbs_t * g, dist_comm_t * c,
 int dist_gibbs_partition_by_value(dist_gibbs_t * g, dist_comm_t * c) {
     return guarded([&] {
         DIST_REQUIRE(c && c->valid(), "no communicator");
-        Gibbs & e = *g->impl;
-        DIST_REQUIRE(e.F() == 1 && is_cat(e.feats[0]->sh.kind)
-                         && e.feats[0]->dim() > 0,
-                     "value partitioning takes engines with one categorical "
-                     "feature (DirichletDiscrete, DirichletProcessDiscrete)");
-        DIST_REQUIRE(!e.batch_open, "a batch is open");
-        const int dim = e.feats[0]->dim();
-        DeviceBuf<int32_t> has;
-        has.reserve((size_t)dim * 2, 0);   // [mine | everybody's]
-        if (e.n_rows)
-            LAUNCH(k_value_presence,
-                   std::min<size_t>(e.n_rows, (size_t)2048 * kBlock),
-                   e.values[0], e.n_rows, dim, has.p);
-        HIP_CHECK(hipMemcpyAsync(has.p + dim, has.p, (size_t)dim * 4,
-                                 hipMemcpyDeviceToDevice, stream()));
-        c->all_reduce(has.p + dim, (size_t)dim, COMM_I32, COMM_SUM, stream());
-        std::vector<int32_t> h((size_t)dim * 2);
-        has.download(h.data(), h.size());
-        std::vector<int32_t> owned((size_t)dim);
-        e.present_values = 0;
-        for (int x = 0; x < dim; ++x) {
-            e.present_values += h[x] ? 1 : 0;
-            DIST_REQUIRE(h[(size_t)dim + x] <= 1,
-                         "value " + std::to_string(x) + " has rows on "
-                         + std::to_string(h[(size_t)dim + x])
-                         + " ranks: not a partition by value");
-            // (a value nobody has rows of: its cells never change; rank 0's)
-            owned[x] = h[x] || (h[(size_t)dim + x] == 0 && c->rank == 0);
-        }
-        e.owned_values.upload(owned.data(), owned.size());
-        e.value_partitioned = true;
-        dist::sync();
+        g->impl->partition_by_value(c);
     });
 }
 int dist_gibbs_gather_cells(dist_gibbs_t * g, dist_comm_t * c) {
     return guarded([&] {
         DIST_REQUIRE(c && c->valid(), "no communicator");
-        Gibbs & e = *g->impl.read();
-        DIST_REQUIRE(e.value_partitioned, "not a value-partitioned engine");
-        DIST_REQUIRE(!e.batch_open, "a batch is open");
-        const int dim = e.feats[0]->dim();
-        const size_t cells = (size_t)e.K() * dim;
-        DeviceBuf<int32_t> image;
-        image.reserve(std::max<size_t>(cells, 1), 0);
-        if (cells)
-            LAUNCH(k_owned_cells, cells, e.feats[0]->cnt.p, e.owned_values.p,
-                   cells, dim, image.p);
-        c->all_reduce(image.p, cells, COMM_I32, COMM_SUM, stream());
-        if (cells)
-            HIP_CHECK(hipMemcpyAsync(e.feats[0]->cnt.p, image.p, cells * 4,
-                                     hipMemcpyDeviceToDevice, stream()));
-        e.cells_partial = false;
-        e.rebuild_caches();
-        dist::sync();
+        g->impl.read()->gather_cells(c);
     });
 }
 int dist_gibbs_comm_volume(dist_gibbs_t * g, uint64_t out[4], int reset) {
@@ -6136,82 +6236,8 @@ int dist_gibbs_sweep_sequential_many(dist_gibbs_t * const * engines, size_t m,
                                      size_t row_begin, size_t row_end,
                                      uint32_t * rng_states) {
     return guarded([&] {
-        DIST_REQUIRE(m == 0 || (engines && rng_states), "null argument");
-        if (!m) return;
-        std::vector<Gibbs *> e(m);
-        for (size_t i = 0; i < m; ++i) {
-            DIST_REQUIRE(engines[i], "null engine");
-            e[i] = &*engines[i]->impl;   // (settles, forgets a sharded run)
-            for (size_t j = 0; j < i; ++j)
-                DIST_REQUIRE(e[j] != e[i], "the same engine twice");
-            DIST_REQUIRE(e[i]->F() == e[0]->F(), "engines of one feature list");
-            for (int f = 0; f < e[0]->F(); ++f)
-                DIST_REQUIRE(e[i]->feats[f]->sh.kind == e[0]->feats[f]->sh.kind,
-                             "engines of one feature list");
-        }
-        // chains whose group count is beyond the kernel's strips (or with the
-        // kernel switched off) take their own path, one after the other
-        std::vector<size_t> at(m, row_begin);
-        std::vector<size_t> todo;
-        for (size_t i = 0; i < m; ++i) {
-            if (e[i]->chain_fits()) {
-                todo.push_back(i);
-            } else {
-                e[i]->sweep_sequential(row_begin, row_end, &rng_states[i]);
-                at[i] = row_end;
-            }
-        }
-        std::vector<ChainArgs> args;
-        while (!todo.empty()) {
-            args.clear();
-            size_t lds = 0;
-            for (size_t i : todo) {
-                args.push_back(e[i]->chain_prepare(at[i], row_end,
-                                                   rng_states[i]));
-                lds = std::max(lds, e[i]->chain_lds_bytes());
-            }
-            Gibbs & first = *e[todo[0]];
-            first.chain_args.upload(args.data(), args.size());
-            Gibbs::ChainsLaunch L{first.chain_args.p, (unsigned)todo.size(),
-                                  lds};
-            first.dispatch(L);
-            first.chain_launches += 1;
-            // every engine's small downloads queued, then ONE wait
-            std::vector<size_t> slot_at(todo.size());
-            size_t slots = 0;
-            for (size_t j = 0; j < todo.size(); ++j) {
-                slot_at[j] = slots;
-                slots += (e[todo[j]]->chain_slot_bytes() + 63) & ~(size_t)63;
-            }
-            char * pinned = Gibbs::chain_pinned(std::max<size_t>(slots, 64));
-            for (size_t j = 0; j < todo.size(); ++j)
-                e[todo[j]]->chain_collect_enqueue(
-                    pinned + slot_at[j],
-                    e[todo[j]]->K() + Gibbs::kChainRoom);
-            HIP_CHECK(hipStreamSynchronize(stream()));
-            std::vector<size_t> again;
-            for (size_t j = 0; j < todo.size(); ++j) {
-                const size_t i = todo[j];
-                const ChainResult res =
-                    e[i]->chain_collect_finish(pinned + slot_at[j]);
-                DIST_REQUIRE(res.rows_done > 0 || res.event != 3
-                                 || at[i] >= row_end,
-                             "internal: the chain kernel found no room");
-                rng_states[i] = res.rng_state;
-                at[i] += res.rows_done;
-                // (out of room, or a group count beyond the strips now)
-                if (at[i] < row_end) {
-                    if (e[i]->chain_fits()) {
-                        again.push_back(i);
-                    } else {
-                        e[i]->sweep_sequential(at[i], row_end, &rng_states[i]);
-                        at[i] = row_end;
-                    }
-                }
-            }
-            todo.swap(again);
-        }
-        dist::sync();
+        Gibbs::sweep_sequential_many(engines, m, row_begin, row_end,
+                                     rng_states);
     });
 }
 int dist_gibbs_batch_sample(dist_gibbs_t * g, size_t row_begin, size_t row_end,
@@ -6512,162 +6538,144 @@ int dist_gibbs_sharded_device_normalise_ok(const dist_gibbs_t * g,
         *ok_out = g->impl.read()->async_eligible_sharded(n_batches, batch_rows) ? 1 : 0;
     });
 }
+// One row per option: the public ones (include/distributions_hip.h documents
+// them) and the tests' hooks, spelled "debug.<name>": each forces a kernel
+// variant the library otherwise picks by itself, and none changes a result.
+struct GibbsOption {
+    const char * name;
+    bool hook;
+    int lo, hi;           // accepted: lo <= value <= hi and, if set, ok(value)
+    bool (*ok)(int);
+    const char * accepts; // ... in words, for the error
+    int Gibbs::* member;
+    bool drops_ranges;    // cached ranges were built by the old value
+};
+static const GibbsOption kGibbsOptions[] = {
+    {"value_sorted", false, 0, 2, nullptr, "0, 1 or 2",
+     &Gibbs::value_sorted_mode, false},
+    // the table-free value-sorted kernel: 0 never, 1 auto, 2 always
+    // (cached ranges chose their apply chunks by it)
+    {"value_stream", false, 0, 2, nullptr, "0, 1 or 2",
+     &Gibbs::value_stream_mode, true},
+    // k_vs_narrow for launches that cannot fill the chip: 0 never, 1 auto,
+    // 2 whenever the vectors fit its LDS (cached ranges carry their tile
+    // lists)
+    {"narrow_tiles", false, 0, 2, nullptr, "0, 1 or 2", &Gibbs::narrow_mode,
+     true},
+    // sweeps whose batches all take the value-sorted path normalise the
+    // group set on the device (no host round trip per batch): 0 never, 1
+    // where it applies (2, the default, is accepted as 1)
+    {"device_normalise", false, 0, 2, nullptr, "0, 1 or 2",
+     &Gibbs::device_normalise_mode, false},
+    // dist_gibbs_sweep_sharded may normalise on the device: set on EVERY
+    // rank or on none (engine.ShardedGibbs agrees on it)
+    {"sharded_device_normalise", false, 0, 1, nullptr, "0 or 1",
+     &Gibbs::sharded_device_normalise, false},
+    // device-normalised runs of the value-sorted path: 1 (default) group
+    // set, caches and per-value tables in ONE launch between two batches
+    // (k_vs_tables), the handed-over rows inside k_vs_apply; 0 the separate
+    // launches
+    {"fused_tables", false, 0, 1, nullptr, "0 or 1",
+     &Gibbs::fused_tables_mode, false},
+    // HIP events around the score+sample kernel of every n-th batch feed
+    // dist_gibbs_kernel_stats: 1 (default) all, 0 none
+    {"kernel_timing", false, 0, INT_MAX, nullptr, ">= 0",
+     &Gibbs::kernel_timing, false},
+    {"phase_timing", false, 0, 1, nullptr, "0 or 1", &Gibbs::phase_timing,
+     false},
+    {"float_stats", false, 0, 1, nullptr, "0 ordered, 1 merged",
+     &Gibbs::float_stats_mode, false},
+    {"sampling", false, 0, 1, nullptr, "0 exact, 1 scan",
+     &Gibbs::sampling_mode, false},
+    // ---- hooks ----
+    // 2 (default): k_chains, structural steps on the device; 1: the chain
+    // kernel that returns to the host at every structural step; 0: every
+    // row as a batch of one
+    {"sequential_chain", true, 0, 2, nullptr, "0, 1 or 2",
+     &Gibbs::sequential_mode, false},
+    // launches of at least this many value tiles start each tile's total
+    // from the per-value running sums (a tuning knob: results do not depend
+    // on it)
+    {"running_sums_min_tiles", true, 0, INT_MAX, nullptr, ">= 0",
+     &Gibbs::running_sums_min_tiles, false},
+    // k_vs_narrow's instance: 0 by launch size, 4 or 8 float4s
+    {"narrow_read_ahead", true, 0, 8,
+     [](int v) { return v == 0 || v == 4 || v == 8; }, "0, 4 or 8",
+     &Gibbs::narrow_read_ahead, false},
+    // k_vs_stream keeps the first pass's likelihoods for the second in a
+    // scratch row per tile (1, default) or computes them again
+    {"stream_scratch", true, 0, 1, nullptr, "0 or 1",
+     &Gibbs::stream_scratch_mode, false},
+    // general rows: 3 k_rows_scratch (default), 0 k_sweep_program (what
+    // feature lists beyond k_rows_scratch's table take anyway)
+    {"rows_scratch", true, 0, 3, [](int v) { return v == 0 || v == 3; },
+     "0 or 3", &Gibbs::rows_scratch_mode, false},
+    {"rows_scratch_lds_log", true, 0, 1, nullptr, "0 or 1",
+     &Gibbs::rows_scratch_lds_log, false},
+    {"rows_scratch_block", true, 64, kScratchMaxBlock,
+     [](int v) { return v % 64 == 0; }, "a multiple of 64 up to 1024",
+     &Gibbs::rows_scratch_block, false},
+    // general rows: the leading discrete features' scores from a
+    // per-(joint value, group) table, rows sorted by joint value (2:
+    // whenever the joint domain is no larger than the batch)
+    {"rows_fold", true, 0, 2, nullptr, "0, 1 or 2", &Gibbs::rows_fold_mode,
+     false},
+    // general rows' integer statistics: 1 (default) the whole image in LDS
+    // and a staging matrix where it fits, 0 global atomics on the
+    // categorical cells
+    {"apply_stage", true, 0, 1, nullptr, "0 or 1", &Gibbs::apply_stage_mode,
+     false},
+    // 1 (default): every batch outside the value-sorted path is scored by
+    // the program kernels when its tables exist
+    {"program_all", true, 0, 1, nullptr, "0 or 1", &Gibbs::program_all,
+     false},
+    // wave priorities by phase: 0 none, else 0x10000 | four levels
+    {"sample_prio", true, 0, 0x1ffff,
+     [](int v) { return v == 0 || (v >> 16) == 1; }, "0 or 0x1abcd",
+     &Gibbs::sample_prio_mode, false},
+    {"rows_prio", true, 0, 0x1ffff,
+     [](int v) { return v == 0 || (v >> 16) == 1; }, "0 or 0x1abcd",
+     &Gibbs::rows_prio_mode, false},
+    // k_vs_apply samples a chunk's few handed-over rows while its other
+    // waves add up the moves (1, default) or before (0)
+    {"apply_overlap", true, 0, 1, nullptr, "0 or 1",
+     &Gibbs::apply_overlap_mode, false},
+    // a device-normalised run covers at most this many batches (a whole
+    // number of passes, at least one); 0: as many as fit
+    {"run_batches_cap", true, 0, INT_MAX, nullptr, ">= 0",
+     &Gibbs::run_batches_cap, false},
+    // k_vs_tables folds every (value, group) cell's sampling total and the
+    // tiles skip their total pass: 0 never, 1 where the library chooses
+    // (default), 2 whenever k_vs_tables runs
+    {"shared_totals", true, 0, 2, nullptr, "0, 1 or 2",
+     &Gibbs::shared_totals_mode, false},
+    // the most (row, group) work-items one k_score_rows launch takes
+    // (default 2^30, under the 2^32 of a 1-D grid)
+    {"score_rows_chunk", true, 1, INT_MAX, nullptr, "> 0",
+     &Gibbs::score_rows_chunk, false},
+    // the most query rows one k_predict launch takes (default 2^22)
+    {"predict_chunk", true, 1, INT_MAX, nullptr, "> 0",
+     &Gibbs::predict_chunk, false},
+};
 int dist_gibbs_set_option(dist_gibbs_t * g, const char * name, int value) {
     return guarded([&] {
-        // The public options first (include/distributions_hip.h lists them);
-        // "debug.<name>" are the tests' hooks: each forces a kernel variant
-        // the library otherwise picks by itself, and none changes a result.
         std::string key(name);
         const bool hook = key.compare(0, 6, "debug.") == 0;
         if (hook) key = key.substr(6);
-        static const char * const hooks[] = {
-            "sequential_chain", "running_sums_min_tiles", "narrow_read_ahead",
-            "stream_scratch", "rows_scratch", "rows_scratch_lds_log",
-            "rows_scratch_block", "rows_fold", "apply_stage", "program_all",
-            "sample_prio", "rows_prio", "apply_overlap", "run_batches_cap",
-            "shared_totals", "score_rows_chunk", "predict_chunk"};
-        bool is_hook = false;
-        for (const char * h : hooks) is_hook = is_hook || key == h;
+        const GibbsOption * o = nullptr;
+        for (const GibbsOption & row : kGibbsOptions)
+            if (key == row.name) o = &row;
+        const bool is_hook = o && o->hook;
         DIST_REQUIRE(hook == is_hook,
                      is_hook ? "a test hook: spell it debug." + key
                              : "unknown option debug." + key);
-        if (key == "sample_prio" || key == "rows_prio") {
-            // wave priorities by phase: 0 none, else 0x10000 | four levels
-            DIST_REQUIRE(value == 0 || (value >> 16) == 1,
-                         "sample_prio / rows_prio: 0 or 0x1abcd");
-            (key == "sample_prio" ? g->impl->sample_prio_mode
-                                  : g->impl->rows_prio_mode) = value;
-        } else if (key == "run_batches_cap") {
-            // a device-normalised run covers at most this many batches (a
-            // whole number of passes, at least one); 0: as many as fit
-            DIST_REQUIRE(value >= 0, "run_batches_cap: >= 0");
-            g->impl->run_batches_cap = value;
-        } else if (key == "apply_overlap") {
-            // k_vs_apply samples a chunk's few handed-over rows while its
-            // other waves add up the moves (1, default) or before (0)
-            DIST_REQUIRE(value == 0 || value == 1, "apply_overlap: 0 or 1");
-            g->impl->apply_overlap_mode = value;
-        } else if (key == "value_sorted") {
-            DIST_REQUIRE(value >= 0 && value <= 2, "value_sorted: 0, 1 or 2");
-            g->impl->value_sorted_mode = value;
-        } else if (key == "value_stream") {
-            // the table-free value-sorted kernel: 0 never, 1 auto, 2 always
-            DIST_REQUIRE(value >= 0 && value <= 2, "value_stream: 0, 1 or 2");
-            g->impl->value_stream_mode = value;
-            // (cached ranges chose their apply chunks by it)
-            g->impl->drop_overlapping_caches(0, g->impl->n_rows, false);
-        } else if (key == "narrow_tiles") {
-            // k_vs_narrow for launches that cannot fill the chip: 0 never,
-            // 1 auto, 2 whenever the vectors fit its LDS
-            DIST_REQUIRE(value >= 0 && value <= 2, "narrow_tiles: 0, 1 or 2");
-            g->impl->narrow_mode = value;
-            // (cached ranges carry their tile lists)
-            g->impl->drop_overlapping_caches(0, g->impl->n_rows, false);
-        } else if (key == "stream_scratch") {
-            // k_vs_stream keeps the first pass's likelihoods for the second
-            // in a scratch row per tile (1, default) or computes them again
-            DIST_REQUIRE(value == 0 || value == 1, "stream_scratch: 0 or 1");
-            g->impl->stream_scratch_mode = value;
-        } else if (key == "kernel_timing") {
-            // HIP events around the score+sample kernel of every n-th batch
-            // feed dist_gibbs_kernel_stats: 1 (default) all, 0 none
-            DIST_REQUIRE(value >= 0, "kernel_timing: >= 0");
-            g->impl->kernel_timing = value;
-        } else if (key == "narrow_read_ahead") {
-            // k_vs_narrow's instance: 0 by launch size, 4 or 8 float4s
-            DIST_REQUIRE(value == 0 || value == 4 || value == 8,
-                         "narrow_read_ahead: 0, 4 or 8");
-            g->impl->narrow_read_ahead = value;
-        } else if (key == "device_normalise") {
-            // sweeps whose batches all take the value-sorted path normalise
-            // the group set on the device (no host round trip per batch):
-            // 0 never, 1 where it applies (default; 2 is accepted as 1)
-            DIST_REQUIRE(value >= 0 && value <= 2, "device_normalise: 0, 1 or 2");
-            g->impl->device_normalise_mode = value;
-        } else if (key == "sharded_device_normalise") {
-            // dist_gibbs_sweep_sharded may normalise on the device: set on
-            // EVERY rank or on none (engine.ShardedGibbs agrees on it)
-            DIST_REQUIRE(value == 0 || value == 1,
-                         "sharded_device_normalise: 0 or 1");
-            g->impl->sharded_device_normalise = value != 0;
-        } else if (key == "running_sums_min_tiles") {
-            // launches of at least this many value tiles start each tile's
-            // total from the per-value running sums (a tuning knob: results
-            // do not depend on it)
-            DIST_REQUIRE(value >= 0, "running_sums_min_tiles: >= 0");
-            g->impl->running_sums_min_tiles = value;
-        } else if (key == "score_rows_chunk") {
-            // the most (row, group) work-items one k_score_rows launch
-            // takes (default 2^30, under the 2^32 of a 1-D grid)
-            DIST_REQUIRE(value > 0, "score_rows_chunk: > 0");
-            g->impl->score_rows_chunk = (size_t)value;
-        } else if (key == "predict_chunk") {
-            // the most query rows one k_predict launch takes (default 2^22)
-            DIST_REQUIRE(value > 0, "predict_chunk: > 0");
-            g->impl->predict_chunk = (size_t)value;
-        } else if (key == "shared_totals") {
-            // k_vs_tables folds every (value, group) cell's sampling total
-            // and the tiles skip their total pass: 0 never, 1 where the
-            // library chooses (default), 2 whenever k_vs_tables runs
-            DIST_REQUIRE(value >= 0 && value <= 2, "shared_totals: 0, 1 or 2");
-            g->impl->shared_totals_mode = value;
-        } else if (key == "rows_scratch") {
-            // general rows: 3 k_rows_scratch (default), 0 k_sweep_program
-            // (what feature lists beyond k_rows_scratch's table take anyway)
-            DIST_REQUIRE(value == 0 || value == 3, "rows_scratch: 0 or 3");
-            g->impl->rows_scratch_mode = value;
-        } else if (key == "rows_scratch_lds_log") {
-            DIST_REQUIRE(value == 0 || value == 1,
-                         "rows_scratch_lds_log: 0 or 1");
-            g->impl->rows_scratch_lds_log = value;
-        } else if (key == "rows_scratch_block") {
-            DIST_REQUIRE(value >= 64 && value <= kScratchMaxBlock
-                             && value % 64 == 0,
-                         "rows_scratch_block: a multiple of 64 up to 1024");
-            g->impl->rows_scratch_block = value;
-        } else if (key == "sampling") {
-            DIST_REQUIRE(value == 0 || value == 1, "sampling: 0 exact, 1 scan");
-            g->impl->sampling_mode = value;
-        } else if (key == "phase_timing") {
-            DIST_REQUIRE(value == 0 || value == 1, "phase_timing: 0 or 1");
-            g->impl->phase_timing = value;
-        } else if (key == "float_stats") {
-            DIST_REQUIRE(value == 0 || value == 1,
-                         "float_stats: 0 ordered, 1 merged");
-            g->impl->float_stats_mode = value;
-        } else if (key == "apply_stage") {
-            // general rows' integer statistics: 1 (default) the whole image
-            // in LDS and a staging matrix where it fits, 0 global atomics on
-            // the categorical cells
-            DIST_REQUIRE(value == 0 || value == 1, "apply_stage: 0 or 1");
-            g->impl->apply_stage_mode = value;
-        } else if (key == "rows_fold") {
-            // general rows: the leading discrete features' scores from a
-            // per-(joint value, group) table, rows sorted by joint value
-            // (2: whenever the joint domain is no larger than the batch)
-            DIST_REQUIRE(value >= 0 && value <= 2, "rows_fold: 0, 1 or 2");
-            g->impl->rows_fold_mode = value;
-        } else if (key == "program_all") {
-            // 1 (default): every batch outside the value-sorted path is
-            // scored by the program kernels when its tables exist
-            DIST_REQUIRE(value == 0 || value == 1, "program_all: 0 or 1");
-            g->impl->program_all = value;
-        } else if (key == "fused_tables") {
-            // device-normalised runs of the value-sorted path: 1 (default)
-            // group set, caches and per-value tables in ONE launch between
-            // two batches (k_vs_tables), the handed-over rows inside
-            // k_vs_apply; 0 the separate launches
-            DIST_REQUIRE(value == 0 || value == 1, "fused_tables: 0 or 1");
-            g->impl->fused_tables_mode = value;
-        } else if (key == "sequential_chain") {
-            // 2 (default): k_chains, structural steps on the device; 1:
-            // round 3's kernel (back to the host at every structural step);
-            // 0: every row as a batch of one
-            DIST_REQUIRE(value >= 0 && value <= 2, "sequential_chain: 0, 1 or 2");
-            g->impl->sequential_mode = value;
-        } else {
-            throw Error("unknown option: " + key);
-        }
+        if (!o) throw Error("unknown option: " + key);
+        DIST_REQUIRE(value >= o->lo && value <= o->hi
+                         && (!o->ok || o->ok(value)),
+                     key + ": " + o->accepts);
+        Gibbs & e = *g->impl;   // (settles an open run)
+        e.*(o->member) = value;
+        if (o->drops_ranges) e.drop_overlapping_caches(0, e.n_rows, false);
     });
 }
 int dist_gibbs_path_counts(const dist_gibbs_t * g, uint64_t * value_sorted,

@@ -11,6 +11,15 @@ namespace dist {
 constexpr int kBlock = 256;
 constexpr int kMaxF = DIST_MAX_FEATURES;
 
+// Dynamic LDS.  Each kernel that takes some has its size function beside it
+// (<kernel>_lds): the host's eligibility tests and launches call that and
+// compute no byte count of their own.  Up to kLdsNoOptIn bytes a launch needs
+// nothing more; beyond, the kernel instance opts in first (launch_lds,
+// dist_hip.hip).  A 1024-thread workgroup may take most of the CU's 160 KiB:
+// kLdsWorkgroupLimit.
+constexpr size_t kLdsNoOptIn = 64 * 1024;
+constexpr size_t kLdsWorkgroupLimit = 144 * 1024;
+
 }  // namespace dist
 
 // (split by path; the order matters: later parts use the earlier ones)

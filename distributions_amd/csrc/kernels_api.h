@@ -396,6 +396,12 @@ struct NormaliseParams {
     DevState * dev;
     int n_empty;         // invariant of the chain
 };
+// LDS of k_normalise: K + 2 ints and K / 2 + 1 slot pairs; the one workgroup
+// has the CU to itself and may take this much
+constexpr size_t kNormaliseLdsLimit = 150 * 1024;
+constexpr size_t normalise_lds(int K) {
+    return ((size_t)K + 2) * 4 + ((size_t)K / 2 + 1) * 8;
+}
 __global__ __launch_bounds__(kNormaliseBlock) void k_normalise(
         NormaliseParams P) {
     // [K + 2] emptied-before (padded to 8 bytes) | [K / 2 + 1] {dst, src}

@@ -58,6 +58,10 @@ __global__ void k_apply_moves(SweepParams P, StatImage img,
 // Integer additions: the result does not depend on the order.
 constexpr int kApplyLdsBlock = 1024;
 constexpr int kApplyLdsRows = 8192;
+// (its LDS: the sizes' and F features' two totals, K ints each)
+constexpr size_t apply_moves_lds(int F, int K) {
+    return (size_t)(1 + 2 * F) * K * sizeof(int);
+}
 __global__ __launch_bounds__(kApplyLdsBlock) void k_apply_moves_lds(
         SweepParams P, StatImage img, const uint32_t * __restrict__ p2g,
         uint32_t * __restrict__ assign) {
@@ -136,6 +140,9 @@ struct StageLayout {
     int dim[kMaxF];
     int words;
 };
+constexpr size_t apply_moves_stage_lds(size_t words) {
+    return words * sizeof(int);
+}
 __global__ __launch_bounds__(kApplyLdsBlock) void k_apply_moves_stage(
         SweepParams P, StageLayout L, int32_t * __restrict__ stage,
         const uint32_t * __restrict__ p2g, uint32_t * __restrict__ assign) {
@@ -316,6 +323,9 @@ struct MergeLayout {
     int words;                // doubles per image
     int K;
 };
+constexpr size_t merge_float_lds(int words) {
+    return (size_t)words * sizeof(double);
+}
 __global__ __launch_bounds__(kApplyLdsBlock) void k_merge_float_moves(
         SweepParams P, MergeLayout L, const uint32_t * __restrict__ old_slot,
         const uint32_t * __restrict__ new_slot, double * __restrict__ stage) {
@@ -478,6 +488,12 @@ __global__ void k_zero_ordered_stats(SlaveView s, int K) {
 constexpr int kCsBlock = 256;            // threads per workgroup
 constexpr int kCsEvents = 4096;          // events per workgroup: 1024 per wave
 constexpr int kCsMaxKeys = 7000;         // (the scatter keeps 5 x n_keys in LDS)
+// (LDS: the histogram one row of n_keys counters, the scatter the bases and
+// a row per wave)
+constexpr size_t cs_hist_lds(int n_keys) { return (size_t)n_keys * 4; }
+constexpr size_t cs_scatter_lds(int n_keys) {
+    return (size_t)(kCsBlock / 64 + 1) * n_keys * 4;
+}
 __device__ __forceinline__ uint32_t cs_event_key(
         const uint32_t * __restrict__ old_packed,
         const uint32_t * __restrict__ new_packed, size_t e, uint32_t pad_key) {

@@ -1324,6 +1324,15 @@ __device__ __forceinline__ void wave_row_update(
 // (every lane computes the same sum over LDS broadcasts).  Same float
 // operations as the lane-per-row kernel, a row's latency drops from ~3K
 // dependent gather round trips to ~2K LDS-fed adds.
+// (LDS: a strip of K floats, padded to whole waves, per wave; what the strip
+// kernels may take of it leaves room for their static tables under 64 KiB)
+constexpr size_t kLdsStripLimit = 60 * 1024;
+constexpr size_t rows_strip_lds(int K) {
+    return (size_t)((K + 63) & ~63) * sizeof(float);
+}
+constexpr size_t rows_wave_lds(int K) {
+    return (size_t)(kBlock / 64) * rows_strip_lds(K);
+}
 template <int KIND0, int KIND1, int NF>
 __global__ __launch_bounds__(kBlock) void k_rows_wave(SweepParams P) {
     extern __shared__ __attribute__((aligned(16))) float wave_lds[];
@@ -1417,6 +1426,8 @@ __device__ __forceinline__ void chain_value_op(const SlaveView & s, int k,
 // sample, add; nothing is removed, the sample size grows with every row (so
 // the driver's score is shifted[k] - fast_log(sample_size + alpha) afresh per
 // row, clustering.hpp:195-208); 2: with the clustering model's score alone.
+// (LDS: one strip)
+constexpr size_t chain_rows_lds(int K) { return rows_strip_lds(K); }
 template <int KIND0, int KIND1, int NF, int INIT = 0>
 __global__ __launch_bounds__(kBlock) void k_chain_rows(
         SweepParams P, float * __restrict__ base, int32_t * counts,
@@ -1639,6 +1650,11 @@ __device__ __forceinline__ void lds_barrier() {
 // fastest single chain) or read where it lies (L2; the three logarithms of
 // an update then cost it a second trip to memory, but four chains fit a CU:
 // launches of more than two chains per CU take this instance)
+// (dynamic LDS: scores and group sizes of the `room` slots the launch may
+// grow into, padded to whole waves)
+constexpr size_t chains_lds(int room) {
+    return (size_t)((room + 63) & ~63) * 8;
+}
 template <int KIND0, int KIND1, int NF, bool LOGL>
 __global__ __launch_bounds__(kBlock)
 __attribute__((amdgpu_waves_per_eu(LOGL ? 2 : 4, LOGL ? 2 : 4)))

@@ -144,6 +144,10 @@ __device__ __forceinline__ bool vs_group_has_value(const SlaveView & v, int g,
     return (x ? v.i0[g] : v.i1[g]) >= 1;   // BB: heads / tails
 }
 
+// (LDS: a value's two vectors while the running sums are built, else none)
+constexpr size_t vs_prepare_lds(int Kpad, bool running_sums) {
+    return running_sums ? (size_t)Kpad * 8 : 0;
+}
 template <int KIND>
 __global__ __launch_bounds__(kBlock) void k_vs_prepare(
         SweepParams P, VsTables T, uint32_t * deferred_count,
@@ -516,6 +520,8 @@ __device__ __forceinline__ void vs_tables_totals(
     }
 }
 
+// (LDS: four words per group of the padded bound, see tb_lds below)
+constexpr size_t vs_tables_lds(int Kpad) { return ((size_t)Kpad * 4 + 2) * 4; }
 template <int KIND>
 __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
                                                             VsTables T) {
@@ -1399,6 +1405,13 @@ struct VsScanTables {
 constexpr int kVsScanBlock = 256;
 constexpr int kVsScanCoarse = 64;
 
+// (VsScanTables::lds_scores: a value's scores stay in LDS up to 48 KiB)
+constexpr bool vs_scan_scores_in_lds(int Kpad) {
+    return (size_t)Kpad * 4 <= 48 * 1024;
+}
+constexpr size_t vs_scan_prepare_lds(int Kpad, bool lds_scores) {
+    return lds_scores ? (size_t)Kpad * 4 : 0;
+}
 template <int KIND>
 __global__ __launch_bounds__(kVsScanBlock) void k_vs_scan_prepare(
         SweepParams P, VsScanTables T, uint32_t * deferred_count,
@@ -1677,6 +1690,11 @@ __device__ __forceinline__ int vs_narrow_row(
     return f < K - 1 ? f : K - 1;
 }
 
+// (LDS: both vectors of the value over the groups this launch walks, and
+// the read-ahead's overrun)
+constexpr size_t vs_narrow_lds(int Kuse) {
+    return 2 * ((size_t)Kuse + 2 * kVsUnroll) * sizeof(float);
+}
 // HQ: float4s read ahead per vector (vs_narrow_row)
 template <int KIND, int HQ>
 __global__ __launch_bounds__(64) void k_vs_narrow(
@@ -2422,6 +2440,20 @@ constexpr int kVsApplyBlock = 1024;   // one workgroup per chunk: keep the CU bu
 // so almost every chunk of the likelihood vector is free of own slots (see
 // vs_sum_and_scan).  The order is a performance hint only: results do not
 // depend on it.
+// LDS by the bound k on the group count the host sized the launch with (the
+// kernel lays it out by the true count, which is no larger).  Plain form:
+// delta[k].  Sorting form: delta, hist, a partial per wave, four strips of
+// kVsApplyRows words and four words of scalars; with room for up to four
+// handed-over rows' strips of scores beside them where `overlap` is set.
+constexpr size_t vs_apply_plain_lds(size_t k) { return k * 4; }
+constexpr size_t vs_apply_sort_lds(size_t k) {
+    return (k * 2 + kVsApplyBlock / 64 + 4 * kVsApplyRows + 4) * 4;
+}
+constexpr size_t vs_apply_overlap_lds(size_t k) {
+    const size_t with_strips =
+        vs_apply_sort_lds(k) + 4 * ((k + 63) & ~(size_t)63) * 4;
+    return with_strips < kLdsWorkgroupLimit ? with_strips : kLdsWorkgroupLimit;
+}
 template <int KIND, bool SORT>
 __global__ __launch_bounds__(kVsApplyBlock) void k_vs_apply(
         SweepParams P, StatImage img, const VsTile * __restrict__ chunks,

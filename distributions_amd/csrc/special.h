@@ -33,7 +33,7 @@ struct Tables {
     uint32_t exp_ab[2];          // vendor/fmath.hpp:154-160: 1024/logf(2), logf(2)/1024
 };
 
-extern __device__ Tables g_tables_dev;   // defined in kernels.hip
+extern __device__ Tables g_tables_dev;   // defined in dist_hip.hip
 extern const Tables * g_tables_host;     // host copy
 
 // glibc lgammaf values for the few arguments below 2.5 that a model can

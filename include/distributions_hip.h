@@ -650,7 +650,7 @@ int dist_gibbs_sharded_device_normalise_ok(const dist_gibbs_t * g,
  *  "narrow_tiles"  0 never | 1 auto (default: launches too small to fill the
  *      chip take tiles of 64 rows, vectors from LDS: k_vs_narrow) | 2 whenever
  *      the vectors fit.  test_gpu_sweep.py::test_batch_sweeps_bit_exact (modes 4, 5)
- *  "device_normalise"  1 (default; 2 accepted) sweeps that stay on the
+ *  "device_normalise"  1 | 2 (default; the same as 1) sweeps that stay on the
  *      value-sorted path with integer statistics normalise the group set on
  *      the device, no host round trip per batch; such a run stays OPEN when
  *      dist_gibbs_sweep / dist_gibbs_sweep_sharded return (the next sweep of
@@ -703,30 +703,50 @@ int dist_gibbs_sharded_device_normalise_ok(const dist_gibbs_t * g,
  * Test hooks, spelled "debug.<name>": each forces a kernel variant the library
  * otherwise picks by itself, so that the differential fuzz (tools/fuzz.py,
  * tests/test_gpu_fuzz.py) reaches every variant at every size; not for
- * callers, and none changes a result.  sequential_chain (1 the device-resident
- * chain kernel | 0 rows as batches of one), running_sums_min_tiles (launches of
- * at least this many tiles use the per-value running sums and band tiles:
- * 2048), narrow_read_ahead (k_vs_narrow's instance: 0 by launch size | 4 | 8
- * float4s), stream_scratch (k_vs_stream keeps a tile's likelihoods between its
- * passes: 1 | 0 computes them again), rows_scratch (general rows: 3
- * k_rows_scratch | 0 k_sweep_program, which feature lists beyond 64 parameter
- * slots take anyway), rows_scratch_lds_log (FastLog's table in LDS: 1 | 0),
- * rows_scratch_block (threads per workgroup of that kernel: 512), rows_fold
- * (leading discrete features folded into a per-(joint value, group) table:
- * 1 where 128 rows share a value | 2 whenever the joint domain fits | 0),
- * apply_stage (general rows' integer statistics summed in LDS: 1 | 0),
- * program_all (every batch outside the value-sorted path through the
- * per-batch score program: 1 | 0), sample_prio / rows_prio (wave priorities
- * by phase in k_vs_sample + k_vs_stream / k_rows_scratch: 0x13210 set-up,
- * first pass, ..., last pass | 0 none -- the A/B of
- * profiles/r5_wave_priorities.txt), apply_overlap (k_vs_apply samples a
- * chunk's few handed-over rows while its other waves add up the moves: 1 | 0
- * before they do), run_batches_cap (a device-normalised run covers at most
- * this many batches: 0 as many as fit -- tests/test_gpu_native_ranks.py sees a
- * run used up and the ranks agree on the next one), score_rows_chunk (the most
- * (row, group) work-items one dist_gibbs_score_rows_dev launch takes: 2^30),
- * predict_chunk (the most query rows one dist_gibbs_predict launch takes:
- * 2^22).
+ * callers, and none changes a result.  (The library's table of options,
+ * kGibbsOptions in dist_hip.hip, has a row per name listed here;
+ * tests/test_gpu_launch_lds.py holds the two lists together.)
+ *
+ *  "debug.sequential_chain"  2 (default) the exact chain with its structural
+ *      steps on the device (k_chains) | 1 the chain kernel that returns to the
+ *      host at every structural step | 0 rows as batches of one
+ *  "debug.running_sums_min_tiles"  n >= 0: launches of at least this many
+ *      tiles use the per-value running sums and band tiles (2048)
+ *  "debug.narrow_read_ahead"  k_vs_narrow's instance: 0 by launch size
+ *      (default) | 4 | 8 float4s
+ *  "debug.stream_scratch"  k_vs_stream keeps a tile's likelihoods between its
+ *      passes: 1 (default) | 0 computes them again
+ *  "debug.rows_scratch"  general rows: 3 k_rows_scratch (default) | 0
+ *      k_sweep_program, which feature lists beyond 64 parameter slots take
+ *      anyway
+ *  "debug.rows_scratch_lds_log"  FastLog's table in LDS: 1 (default) | 0
+ *  "debug.rows_scratch_block"  threads per workgroup of that kernel: a
+ *      multiple of 64 up to 1024 (512)
+ *  "debug.rows_fold"  leading discrete features folded into a per-(joint
+ *      value, group) table: 1 where 128 rows share a value (default) | 2
+ *      whenever the joint domain fits | 0
+ *  "debug.apply_stage"  general rows' integer statistics summed in LDS: 1
+ *      (default) | 0
+ *  "debug.program_all"  every batch outside the value-sorted path through the
+ *      per-batch score program: 1 (default) | 0
+ *  "debug.sample_prio"  wave priorities by phase in k_vs_sample and
+ *      k_vs_stream: 0x13210 (default: set-up, first pass, ..., last pass) | 0
+ *      none | 0x1abcd -- the A/B of profiles/r5_wave_priorities.txt
+ *  "debug.rows_prio"  the same in k_rows_scratch
+ *  "debug.apply_overlap"  k_vs_apply samples a chunk's few handed-over rows
+ *      while its other waves add up the moves: 1 (default) | 0 before they do
+ *  "debug.run_batches_cap"  n >= 0: a device-normalised run covers at most
+ *      this many batches, 0 (default) as many as fit --
+ *      tests/test_gpu_native_ranks.py sees a run used up and the ranks agree
+ *      on the next one
+ *  "debug.shared_totals"  k_vs_tables folds every (value, group) cell's
+ *      sampling total and the tiles skip their total pass: 0 never | 1 where
+ *      the library chooses (default) | 2 whenever k_vs_tables runs.
+ *      tests/test_gpu_shared_totals.py
+ *  "debug.score_rows_chunk"  n > 0: the most (row, group) work-items one
+ *      dist_gibbs_score_rows_dev launch takes (2^30)
+ *  "debug.predict_chunk"  n > 0: the most query rows one dist_gibbs_predict
+ *      launch takes (2^22)
  */
 int dist_gibbs_set_option(dist_gibbs_t * g, const char * name, int value);
 /* how many batches each score+sample kernel has served */

@@ -1,9 +1,12 @@
 # A/B of two BUILDS of the library on one box, alternating: copy the build to compare against to
 # distributions_amd/libdist_base.so (git-ignored) before the gpurun call, then
-#   [CFGS="dd gp"] [STEPS=20] [WARMUP=5] bash tools/ab_lib.sh [bench.py arguments]
+#   [CFGS="dd gp"] [STEPS=20] [WARMUP=5] [LIMIT=300] bash tools/ab_lib.sh [bench.py arguments]
+# (every bench.py run under a time limit of LIMIT seconds; the first run that fails ends the script)
+set -eo pipefail
 L=distributions_amd/libdistributions_hip.so
 cp $L /tmp/new.so; cp distributions_amd/libdist_base.so /tmp/base.so
-run() { python bench.py --steps ${STEPS:-4} --warmup ${WARMUP:-2} --no-breakdown --other-batches= --other-configs= --cpu-rows 8192 "$@" 2>/dev/null | python -c "
+trap 'cp /tmp/new.so $L' EXIT   # (also when a run fails)
+run() { timeout -k 10 ${LIMIT:-300} python bench.py --steps ${STEPS:-4} --warmup ${WARMUP:-2} --no-breakdown --other-batches= --other-configs= --cpu-rows 8192 "$@" 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     l=l.strip()
@@ -16,4 +19,3 @@ for cfg in ${CFGS:-gp_nich gp nich mixed}; do
     cp /tmp/new.so $L; echo -n "$cfg new:  "; run --config $cfg "$@"
   done
 done
-cp /tmp/new.so $L
