@@ -1,5 +1,6 @@
 // Shared host-side plumbing of libdistributions_hip: error reporting, device
-// buffers, one-time table upload.
+// buffers, pinned host buffers and events that free themselves, one-time
+// table upload.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,6 +9,7 @@
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/distributions_hip.h"
@@ -121,6 +123,59 @@ struct DeviceBuf {
             HIP_CHECK(hipMemcpyAsync(host, p, n * sizeof(T),
                                      hipMemcpyDeviceToHost, stream()));
         HIP_CHECK(hipStreamSynchronize(stream()));
+    }
+};
+
+// Pinned host memory that a kernel or an asynchronous copy writes and the host
+// reads, freed with its owner.  Nothing here waits for the device: whoever
+// replaces a buffer that work in flight may still write waits first (the call
+// sites say which do).  A new buffer's contents are not set.
+template <class T>
+struct PinnedBuf {
+    T * p = nullptr;
+    size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf & operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() {
+        if (p) (void)hipHostFree(p);
+    }
+    // exactly n elements, in place of what was there (single objects such as
+    // a DevState, which reserve's headroom of 64 would only waste)
+    void alloc(size_t n, unsigned flags) {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+        HIP_CHECK(hipHostMalloc((void **)&p, n * sizeof(T), flags));
+        cap = n;
+    }
+    // room for n elements, with headroom; true: the buffer is a new one
+    bool reserve(size_t n, unsigned flags) {
+        if (n <= cap) return false;
+        alloc(grow_capacity(n), flags);
+        return true;
+    }
+};
+
+// An event made by the first get(), with the flags given there, and destroyed
+// with its owner.  get() is for the one site that may be the first to need the
+// event; code that runs only after that site reads `e`.
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event & operator=(const Event &) = delete;
+    Event(Event && o) noexcept : e(o.e) { o.e = nullptr; }
+    Event & operator=(Event && o) noexcept {
+        std::swap(e, o.e);
+        return *this;
+    }
+    ~Event() {
+        if (e) (void)hipEventDestroy(e);
+    }
+    hipEvent_t get(unsigned flags = hipEventDefault) {
+        if (!e) HIP_CHECK(hipEventCreateWithFlags(&e, flags));
+        return e;
     }
 };
 

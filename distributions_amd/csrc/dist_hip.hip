@@ -1148,6 +1148,131 @@ static uint64_t mix64(uint64_t x) {
 }
 
 struct Gibbs {
+    // What dist_gibbs_set_option sets: one int per row of kGibbsOptions (the
+    // C ABI's table holds name, accepted values and error text), here with its
+    // default.  The public ones first (include/distributions_hip.h documents
+    // them), then the tests' hooks, spelled "debug.<name>": each forces a
+    // kernel variant the library otherwise picks by itself, and none changes
+    // a result.
+    struct Options {
+        int value_sorted_mode = 1;   // 0 off, 1 auto, 2 always (when eligible)
+        // the table-free form of the value-sorted kernel (k_vs_stream): 0
+        // never, 1 where a value has about a tile per batch, 2 always (cached
+        // ranges chose their apply chunks by it)
+        int value_stream_mode = 1;
+        // launches too small to fill the chip take tiles of 64 rows, one per
+        // lane, and their vectors from LDS (k_vs_narrow): 0 never, 1 below
+        // kVsNarrowBelowTiles regular tiles, 2 whenever the vectors fit
+        // (cached ranges carry their tile lists)
+        int narrow_mode = 1;
+        // (measured, round 4, K = 1024, rows per launch: 400 k 49.5 us against
+        // k_vs_sample's 51.3, 524 k 61.2 / 68.5, 655 k 66.7 / 69.0, 786 k 77.1
+        // / 68.9, 10^6 93.8 / 67.6; Zipf values 524 k 63.4 / 101.9, 786 k 77.7
+        // / 92.1, 10^6 97.5 / 88.2.  At larger K the vectors leave fewer waves
+        // a place in LDS: round 2's bound stays there.)
+        static constexpr uint32_t kVsNarrowBelowTiles = 5600;
+        // sweeps whose batches all take the value-sorted path normalise the
+        // group set on the device (no host round trip per batch): 0 never, 1
+        // where it applies (2: the same; default)
+        int device_normalise_mode = 2;
+        // dist_gibbs_sweep_sharded may normalise on the device: set on EVERY
+        // rank or on none (the ranks agree on it among themselves when a run
+        // is opened, engine.ShardedGibbs)
+        int sharded_device_normalise = 1;
+        // device-normalised runs of the value-sorted path: 1 (default) group
+        // set, caches and per-value tables in ONE launch between two batches
+        // (k_vs_tables), the handed-over rows inside k_vs_apply; 0:
+        // k_normalise + k_batch_finish + k_vs_prepare as three launches (and
+        // the handed-over rows as a fourth)
+        int fused_tables_mode = 1;
+        // The score+sample kernel of a batch sits between two events
+        // (dist_gibbs_kernel_stats).  An event is a packet of its own on the
+        // queue: around every batch they cost the headline workload 8 us of a
+        // sub-sweep's 134 (events attached to the dispatch itself,
+        // hipExtLaunchKernelGGL, cost the same).  n: every n-th batch (1: all,
+        // the default; 0: none).
+        int kernel_timing = 1;
+        // 1: HIP events at the phase boundaries of every device-normalised
+        // sub-sweep: a diagnostic -- six events cost a sub-sweep some 20 us
+        // -- read by dist_gibbs_phase_stats
+        int phase_timing = 0;
+        // 0 the ordered replay (bit-identical to the sequential chain's
+        // running updates; default), 1 merged: binary64 sums per group
+        // (kernels.h, k_merge_float_*; tolerance-level)
+        int float_stats_mode = 0;
+        // 0 exact (the reference's float operations in the reference's order:
+        // bit-identical assignments; the default and the line of record);
+        // 1 scan: tolerance-level sampling (same scores, same draw per row,
+        // the softmax and its inverse CDF by parallel-friendly float
+        // arithmetic)
+        int sampling_mode = 0;
+        // ---- hooks ----
+        // 2 (default): k_chains, structural steps on the device; 1: round 3's
+        // kernel, back to the host at every structural step; 0: every row as
+        // a batch of one
+        int sequential_mode = 2;
+        // launches of at least this many value tiles start each tile's total
+        // from the per-value running sums (a tuning knob: results do not
+        // depend on it; see sample_value_sorted)
+        int running_sums_min_tiles = 2048;
+        // k_vs_narrow's instance, float4s per vector: 0 by launch size, 4 or 8
+        int narrow_read_ahead = 0;
+        // k_vs_stream keeps the first pass's likelihoods for the second in a
+        // scratch row per tile (1, default) or computes them again in the
+        // scan (0)
+        int stream_scratch_mode = 1;
+        // general rows: 3 = k_rows_scratch (default), 0 = k_sweep_program,
+        // the kernel that stays for feature lists k_rows_scratch's table does
+        // not hold (more than 64 parameter slots), kept selectable so that
+        // the tests reach it
+        int rows_scratch_mode = 3;
+        int rows_scratch_lds_log = 1;   // FastLog's table in LDS (NICH scores)
+        int rows_scratch_block = 512;   // threads per workgroup
+        // general rows, folding (kernels.h, FoldSpec): the leading discrete
+        // features' scores from a per-(joint value, group) table, rows sorted
+        // by joint value: 0 off, 1 where the joint domain leaves >=
+        // kFoldRowsPerCode rows per value, 2 whenever the joint domain is no
+        // larger than the batch
+        int rows_fold_mode = 1;
+        static constexpr size_t kFoldRowsPerCode = 128;
+        // general rows' integer statistics: 1 (default) the whole image in
+        // LDS and a staging matrix where it fits, 0 never the all-in-LDS
+        // form: global atomics on the categorical cells
+        int apply_stage_mode = 1;
+        // 1 (default): every batch the value-sorted kernels do not take goes
+        // through the score program when its tables exist (0: only feature
+        // lists without a compile-time instance of k_sweep_sample, as in
+        // round 2)
+        int program_all = 1;
+        // Wave priorities by phase (k_vs_sample, k_vs_stream, k_rows_scratch):
+        // 0 none, else 0x10000 | set-up << 12 | first pass << 8 | ... | last
+        // pass.  A SIMD issues from its oldest ready wave, so at equal
+        // priority its waves finish one after the other and the last ones run
+        // their dependent adds alone; with the earlier phase ahead of the
+        // later one whoever is behind goes first and they end together
+        // (profiles/r5_wave_priorities.txt).
+        int sample_prio_mode = 0x13210;   // VsTables::prio_mode, k_vs_stream
+        int rows_prio_mode = 0x13210;     // RowsArgs::pad
+        // k_vs_apply samples a chunk's few handed-over rows while its other
+        // waves add up the moves (1, default) or before (0)
+        int apply_overlap_mode = 1;
+        // a device-normalised run covers at most this many batches (a whole
+        // number of passes, at least one); 0: as many as fit
+        int run_batches_cap = 0;
+        // k_vs_tables builds every (value, group) cell's sampling total
+        // (VsTables::tot) and the tiles skip their total pass: 0 never, 1
+        // where the running sums would be built (default), 2 whenever
+        // k_vs_tables runs
+        int shared_totals_mode = 1;
+        // k_score_rows takes one work-item per (row, group): a launch covers
+        // at most this many, whole rows each (default 2^30, under the 2^32 of
+        // a 1-D grid)
+        int score_rows_chunk = 1 << 30;
+        // the most query rows one k_predict launch takes, whole rows each
+        int predict_chunk = 1 << 22;
+    };
+    Options opt;
+
     float alpha, d;
     int cluster = 0;        // 0 PitmanYor(alpha, d), 1 LowEntropy(dataset_size)
     int dataset_size = 0;
@@ -1193,15 +1318,12 @@ struct Gibbs {
     bool moves_in_row_order = false;   // old_row/new_row hold the open batch
     bool base_valid = false;           // base[], base_single[], scalars current
     bool cells_fresh = false;          // set by apply_ints, used by batch_finish
-    bool timing_pending = false;
-    int * pinned_counts = nullptr;
-    size_t pinned_cap = 0;
-    unsigned * pinned_seq = nullptr;   // see k_publish_counts
+    PinnedBuf<int> pinned_counts;
+    PinnedBuf<unsigned> pinned_seq;    // see k_publish_counts
     unsigned publish_ticket = 0;
     // (size, ticket) pairs written by k_vs_reduce; pairs_ticket != 0: the
     // sizes of the open batch are on their way there
-    unsigned long long * pinned_pairs = nullptr;
-    size_t pinned_pairs_cap = 0;
+    PinnedBuf<unsigned long long> pinned_pairs;
     unsigned pairs_ticket = 0;
 
     // value-sorted path (single small-domain feature): rows of a batch range
@@ -1280,60 +1402,40 @@ struct Gibbs {
     size_t vs_last = 0;   // where the last look-up found its range
     DeviceBuf<float> vsLA, vsLB, vsM, vsmB, vsPA, vsPB, vsOwn, vsTot;
     DeviceBuf<int> remap_log;   // the batches' swap-removals (kernels.h)
-    // the removal epoch (DevState::pad) the groups' recorded offsets are
-    // stamped with (VsOffsets): carried from one device-normalised run to the
-    // next as long as the host did not re-pack the groups in between
-    uint32_t run_epoch = 0;
-    uint64_t repacked_seen = ~0ull;
     DeviceBuf<int32_t> vs_stage;   // [chunks][K] deltas of the open batch
     DeviceBuf<int> vsBandMode;     // VsTables::band_mode
     DeviceBuf<VsTile> vsBandTile;  // VsTables::band_tile
     DeviceBuf<unsigned long long> vsStamps;   // diagnostics, see VsTables
     DeviceBuf<float> vsScratch;    // k_vs_stream: [tiles][K] likelihoods
-    int stream_scratch_mode = 1;   // 0: recompute them in the scan instead
     DeviceBuf<ChainResult> chain_result;
-    DeviceBuf<int32_t> delta_image;         // dist_gibbs_sweep_sharded
-    // (what its header words hold: sharded_header's tag, 0 = nothing)
-    uint64_t delta_header_tag = 0;
-    unsigned * comm_fault = nullptr;        // pinned: raised by k_add_words
-    uint64_t comm_words_total = 0, comm_collectives = 0, comm_words_last = 0,
-             comm_words_max = 0;
-    // dist_gibbs_partition_by_value: this rank's rows carry values no other
-    // rank's rows do, so the cells cnt[.][x] of its values are its own and
-    // never travel; cells_partial: the OTHER values' cells here are stale
-    // (dist_gibbs_gather_cells makes the replicas whole again)
-    bool value_partitioned = false, cells_partial = false;
-    size_t present_values = 0;              // values with rows on this rank
-    DeviceBuf<int32_t> owned_values;        // [dim] 1: this rank's
-    void require_whole(const char * what) const {
-        DIST_REQUIRE(!cells_partial,
-                     std::string(what) + ": the cells of other ranks' values "
-                     "are stale on a value-partitioned rank "
-                     "(dist_gibbs_gather_cells first)");
-    }
+    // What dist_gibbs_sweep_sharded exchanges with the other ranks, and what
+    // this rank knows about its part of the data.
+    struct Exchange {
+        DeviceBuf<int32_t> delta_image;
+        // (what its header words hold: sharded_header's tag, 0 = nothing)
+        uint64_t delta_header_tag = 0;
+        PinnedBuf<unsigned> comm_fault;     // raised by k_add_words
+        DeviceBuf<int> agree_flag;
+        uint64_t comm_words_total = 0, comm_collectives = 0,
+                 comm_words_last = 0, comm_words_max = 0;
+        // dist_gibbs_partition_by_value: this rank's rows carry values no
+        // other rank's rows do, so the cells cnt[.][x] of its values are its
+        // own and never travel; cells_partial: the OTHER values' cells here
+        // are stale (dist_gibbs_gather_cells makes the replicas whole again)
+        bool value_partitioned = false, cells_partial = false;
+        size_t present_values = 0;          // values with rows on this rank
+        DeviceBuf<int32_t> owned_values;    // [dim] 1: this rank's
+        void require_whole(const char * what) const {
+            DIST_REQUIRE(!cells_partial,
+                         std::string(what) + ": the cells of other ranks' "
+                         "values are stale on a value-partitioned rank "
+                         "(dist_gibbs_gather_cells first)");
+        }
+    };
+    Exchange ex;
     DeviceBuf<float> own_score;             // k_row_prepass
-    // general rows: 3 = k_rows_scratch (default), 0 = k_sweep_program, the
-    // kernel that stays for feature lists k_rows_scratch's table does not
-    // hold (more than 64 parameter slots), kept selectable so that the tests
-    // reach it
-    int rows_scratch_mode = 3;
-    int rows_scratch_lds_log = 1;     // FastLog's table in LDS where NICH scores
-    int rows_scratch_block = 512;     // threads per workgroup
-    // 1: every batch the value-sorted kernels do not take goes through the
-    // score program when its tables exist (0: only feature lists without a
-    // compile-time instance of k_sweep_sample, as in round 2)
-    int program_all = 1;
     DeviceBuf<float> rows_gtab;             // [W][Kpad], see k_rows_gtab
     DeviceBuf<float2> rows_snap;            // k_rows_scratch, scan mode
-    // 0 exact (the reference's float operations in the reference's order:
-    // bit-identical assignments; the default and the line of record);
-    // 1 scan: tolerance-level sampling (same scores, same draw per row, the
-    // softmax and its inverse CDF by parallel-friendly float arithmetic)
-    int sampling_mode = 0;
-    // folding (kernels.h, FoldSpec): 0 off, 1 where the joint domain of the
-    // leading discrete features leaves >= kFoldRowsPerCode rows per value
-    int rows_fold_mode = 1;
-    static constexpr size_t kFoldRowsPerCode = 128;
     struct FoldCache {
         size_t r0 = 0, r1 = 0;
         int n_fold = 0;
@@ -1378,48 +1480,17 @@ struct Gibbs {
         return *fold_cache.back();
     }
     uint64_t scratch_batches = 0;
-    // 2: k_chains (structural steps on the device); 1: round 3's kernel, back
-    // to the host at every structural step; 0: every row as a batch of one
-    int sequential_mode = 2;
     DeviceBuf<int> vsArg;
     DeviceBuf<uint32_t> deferred, deferred_count;
-    int value_sorted_mode = 1;   // 0 off, 1 auto, 2 always (when eligible)
-    // the table-free form of the value-sorted kernel (k_vs_stream): 0 never,
-    // 1 where a value has about a tile per batch, 2 always
-    int value_stream_mode = 1;
     uint64_t stream_batches = 0;
-    // launches too small to fill the chip take tiles of 64 rows, one per lane,
-    // and their vectors from LDS (k_vs_narrow): 0 never, 1 below
-    // kVsNarrowBelowTiles regular tiles, 2 whenever the vectors fit
-    int narrow_mode = 1;
-    int narrow_read_ahead = 0;   // float4s per vector: 0 auto, 4 or 8
-    // Wave priorities by phase (k_vs_sample, k_vs_stream, k_rows_scratch):
-    // 0x10000 | set-up << 12 | first pass << 8 | ... | last pass.  A SIMD
-    // issues from its oldest ready wave, so at equal priority its waves
-    // finish one after the other and the last ones run their dependent adds
-    // alone; with the earlier phase ahead of the later one whoever is behind
-    // goes first and they end together (profiles/r5_wave_priorities.txt).
-    int sample_prio_mode = 0x13210;   // VsTables::prio_mode, k_vs_stream
-    int rows_prio_mode = 0x13210;     // RowsArgs::pad
-    int apply_overlap_mode = 1;       // k_vs_apply: hand-overs beside the adds
     uint64_t narrow_batches = 0;
-    // (measured, round 4, K = 1024, rows per launch: 400 k 49.5 us against
-    // k_vs_sample's 51.3, 524 k 61.2 / 68.5, 655 k 66.7 / 69.0, 786 k 77.1 /
-    // 68.9, 10^6 93.8 / 67.6; Zipf values 524 k 63.4 / 101.9, 786 k 77.7 /
-    // 92.1, 10^6 97.5 / 88.2.  At larger K the vectors leave fewer waves a
-    // place in LDS: round 2's bound stays there.)
-    static constexpr uint32_t kVsNarrowBelowTiles = 5600;
     bool use_narrow(const VsCache & c, int Kpad) const {
-        if (narrow_mode == 0 || Kpad > kVsNarrowMaxK || !c.n_narrow_tiles)
+        if (opt.narrow_mode == 0 || Kpad > kVsNarrowMaxK || !c.n_narrow_tiles)
             return false;
-        return narrow_mode == 2
-               || c.n_tiles < (Kpad <= 1152 ? kVsNarrowBelowTiles : 4100u);
+        return opt.narrow_mode == 2
+               || c.n_tiles < (Kpad <= 1152 ? Options::kVsNarrowBelowTiles
+                                            : 4100u);
     }
-    int running_sums_min_tiles = 2048;   // see sample_value_sorted
-    // k_vs_tables builds every (value, group) cell's sampling total
-    // (VsTables::tot): 0 never, 1 where the running sums would be built
-    // (default), 2 whenever k_vs_tables runs
-    int shared_totals_mode = 1;
     int cu_count_cached = 0;
     int cu_count() {
         if (!cu_count_cached) {
@@ -1438,117 +1509,200 @@ struct Gibbs {
 
     // Device-side normalisation of the group set (k_normalise): a whole sweep
     // is queued without the host looking at the group sizes in between.
-    // While `async_active`, K() is an UPPER BOUND (the host sizes launches and
-    // buffers with it; the kernels read the group count from dev_state) and
-    // the host mirrors (py.counts, tracker) are stale; sweep_async pulls the
-    // state back before it returns.
-    // (two slots: k_vs_tables reads one and writes the other, dev_cur says
-    // which one holds the state of record)
-    DeviceBuf<DevState> dev_state;
-    int dev_cur = 0;
-    DevState * dev_ptr() const { return dev_state.p + dev_cur; }
-    DeviceBuf<int32_t> snap_counts;   // group sizes at batch entry
-    // The fused launch between two batches (k_vs_tables: group set, caches
-    // and per-value tables in one kernel) reads the per-group statistics from
-    // one set of buffers and writes them, normalised, to another: these are
-    // the other set (swapped with the live ones after every such launch).
-    DeviceBuf<int32_t> alt_counts, alt_i0, alt_i1, alt_snap;
-    // 0: k_normalise + k_batch_finish + k_vs_prepare as three launches (and
-    // the handed-over rows as a fourth); 1 (default): k_vs_tables, the
-    // handed-over rows inside k_vs_apply
-    int fused_tables_mode = 1;
+    // While `run.async_active`, K() is an UPPER BOUND (the host sizes launches
+    // and buffers with it; the kernels read the group count from run.dev_state)
+    // and the host mirrors (py.counts, tracker) are stale; sweep_async pulls
+    // the state back before it returns.  Everything such a run keeps between
+    // its batches, its sweeps and -- where this rank closed it itself -- until
+    // it is taken up again:
+    struct Run {
+        // (two slots: k_vs_tables reads one and writes the other, dev_cur
+        // says which one holds the state of record)
+        DeviceBuf<DevState> dev_state;
+        int dev_cur = 0;
+        DevState * dev_ptr() const { return dev_state.p + dev_cur; }
+        DeviceBuf<int32_t> snap_counts;   // group sizes at batch entry
+        // The fused launch between two batches (k_vs_tables: group set,
+        // caches and per-value tables in one kernel) reads the per-group
+        // statistics from one set of buffers and writes them, normalised, to
+        // another: these are the other set (swapped with the live ones after
+        // every such launch).
+        DeviceBuf<int32_t> alt_counts, alt_i0, alt_i1, alt_snap;
+        // the open run's last batch left its group set to the next
+        // k_vs_tables (or to run_pending_finish())
+        bool finish_pending = false;
+        bool async_active = false;
+        uint64_t async_batches = 0;
+        // the removal epoch (DevState::pad) the groups' recorded offsets are
+        // stamped with (VsOffsets): carried from one run to the next as long
+        // as the host did not re-pack the groups in between
+        uint32_t run_epoch = 0;
+        uint64_t repacked_seen = ~0ull;
+        // A run stays open when its sweep returns (the host's mirrors are
+        // pulled by the next call that is not another such sweep: settle()),
+        // so that consecutive sweeps pay for the hand-over of the state once:
+        // room for kAsyncSweeps sweeps like the first is reserved where the
+        // kernels' LDS allows, and async_left counts the batches still
+        // covered.
+        static constexpr size_t kAsyncSweeps = 8;
+        // ... and with the fused launch (whose work follows the per-launch
+        // bound on the group count, k_limit(), not the run's) as many sweeps
+        // as its LDS allows, up to this many batches
+        static constexpr size_t kAsyncMaxBatches = 16384;
+        size_t async_left = 0;
+        int async_K0 = 0;        // the group count the run began with
+        int async_bound_K = 0;   // its bound on the group count
+        hipStream_t async_stream = nullptr;   // the stream it is queued on
+        // The group count is at most k_limit() when a batch of the open run
+        // is sampled: every batch can fill each empty group once.  K_seen is
+        // the device's own count, copied back without waiting for it
+        // (async_peek): the device's state on its way to pinned_state, one
+        // copy in flight at most.
+        size_t run_batches = 0;          // batches sampled in the open run
+        int K_seen = 0;
+        size_t K_seen_batch = 0;
+        PinnedBuf<DevState> pinned_state;
+        Event peek_event;
+        bool peek_pending = false;
+        size_t peek_batch = 0;
+        // a sharded run (dist_gibbs_sweep_sharded) goes on only with the
+        // tiling all ranks agreed on when it was opened
+        size_t sharded_batches = 0, sharded_batch_rows = 0;
+        uint64_t sharded_run_serial = 0;   // runs the ranks agreed to open
+        // A sharded run this rank closed ITSELF between two passes (any look
+        // at the state does: settle) can be taken up again with the bound on
+        // the group count and the batches it had left -- to its peers, who
+        // kept theirs open, it then looks like a run that went on: the same
+        // collectives of the same size (stat_words() follows the bound), and
+        // the same results (closing a run never changes one).  So whether
+        // open runs go on needs no word between the ranks, and no pass begins
+        // with a host round trip.
+        size_t resume_bound = 0, resume_left = 0;   // 0: nothing to take up
+        void forget_resume() { resume_bound = resume_left = 0; }
+        uint64_t resumed_runs = 0;
+        // What the ranks exchange per sub-sweep is sized by the LIVE part of
+        // the group set, not by the run's bound (round 5 sent the bound's
+        // image: 8.4 MB where 1.1 MB were in use): a batch's deltas touch the
+        // groups that existed when it was sampled, and every batch can fill
+        // each empty group once, so batch j of a run that began with K0
+        // groups touches slots below K0 + j * n_empty -- a number every rank
+        // knows without asking (the device's own count, K_seen, arrives
+        // asynchronously and is not).  A rank that closed its run and takes
+        // it up again keeps the origin it shared with its peers.
+        size_t run_origin_K0 = 0, run_origin_done = 0;
+        size_t resume_K0 = 0, resume_done = 0;
+    };
+    Run run;
     uint64_t fused_batches = 0;
-    // the open device-normalised run's last batch left its group set to the
-    // next k_vs_tables (or to finish_pending())
-    bool finish_pending = false;
     bool batch_fused = false;   // the open batch went through k_vs_tables
-    bool async_active = false;
-    // 0 never, 1 where it applies (2: the same; default)
-    int device_normalise_mode = 2;
-    // dist_gibbs_sweep_sharded may normalise on the device (the ranks agree
-    // on it among themselves when a run is opened)
-    int sharded_device_normalise = 1;
-    uint64_t async_batches = 0;
-    std::vector<hipEvent_t> ev_pool;
-
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // The score+sample kernel of a batch sits between two events
-    // (dist_gibbs_kernel_stats).  An event is a packet of its own on the
-    // queue: around every batch they cost the headline workload 8 us of a
-    // sub-sweep's 134 (events attached to the dispatch itself,
-    // hipExtLaunchKernelGGL, cost the same).  "kernel_timing" = n times every
-    // n-th batch (1: all, the default; 0: none).
-    int kernel_timing = 1;
-    uint64_t timing_tick = 0;
-    bool timing_this_batch = true;
-    void mark(hipEvent_t e) {
-        if (timing_this_batch) HIP_CHECK(hipEventRecord(e, stream()));
-    }
-    double kernel_ms = 0.0;
-    uint64_t kernel_launches = 0, kernel_rows = 0;
-    // the all-reduce of dist_gibbs_sweep_sharded between two events, every
-    // kernel_timing-th sub-sweep (dist_gibbs_comm_stats)
-    double comm_ms = 0.0;
-    uint64_t comm_launches = 0, comm_tick = 0;
-    std::vector<hipEvent_t> comm_ev_free;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> comm_ev_pending;
-    hipEvent_t comm_event() {
-        if (comm_ev_free.empty()) {
-            hipEvent_t e = nullptr;
-            HIP_CHECK(hipEventCreate(&e));
+    // What dist_gibbs_kernel_stats, _comm_stats and _phase_stats report, and
+    // the events it is measured with.
+    struct Timing {
+        // The score+sample kernel of a batch sits between two events, on the
+        // batches opt.kernel_timing picks.  The pair in use: own0 and own1,
+        // or a pair of ev_pool while a device-normalised run is open.
+        Event own0, own1;
+        std::vector<Event> ev_pool;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        std::vector<size_t> async_rows;   // rows of each TIMED batch of the run
+        uint64_t timing_tick = 0;
+        bool timing_this_batch = true;
+        bool timing_pending = false;
+        void mark(hipEvent_t e) {
+            if (timing_this_batch) HIP_CHECK(hipEventRecord(e, stream()));
+        }
+        double kernel_ms = 0.0;
+        uint64_t kernel_launches = 0, kernel_rows = 0;
+        // timed batch i of the open run takes pair i of the pool
+        void use_run_pair() {
+            const size_t i = async_rows.size();
+            while (ev_pool.size() < 2 * (i + 1)) {
+                ev_pool.emplace_back();
+                ev_pool.back().get();
+            }
+            ev0 = ev_pool[2 * i].e;
+            ev1 = ev_pool[2 * i + 1].e;
+        }
+        void use_own_pair() {
+            ev0 = own0.get();
+            ev1 = own1.get();
+        }
+        // (call with the stream drained)
+        void collect_run() {
+            for (size_t i = 0; i < async_rows.size(); ++i) {
+                if (!async_rows[i]) continue;
+                float ms = 0.f;
+                HIP_CHECK(hipEventElapsedTime(&ms, ev_pool[2 * i].e,
+                                              ev_pool[2 * i + 1].e));
+                kernel_ms += ms;
+                kernel_launches += 1;
+                kernel_rows += async_rows[i];
+            }
+        }
+        // the all-reduce of dist_gibbs_sweep_sharded between two events,
+        // every opt.kernel_timing-th sub-sweep
+        double comm_ms = 0.0;
+        uint64_t comm_launches = 0, comm_tick = 0;
+        std::vector<Event> comm_ev_free;
+        std::vector<std::pair<Event, Event>> comm_ev_pending;
+        Event comm_event() {
+            Event e;
+            if (!comm_ev_free.empty()) {
+                e = std::move(comm_ev_free.back());
+                comm_ev_free.pop_back();
+            }
+            e.get();
             return e;
         }
-        hipEvent_t e = comm_ev_free.back();
-        comm_ev_free.pop_back();
-        return e;
-    }
-    // "phase_timing" = 1: HIP events at the phase boundaries of every
-    // device-normalised sub-sweep (tables | score+sample | handed-over rows |
-    // statistics | group set + caches): a diagnostic -- six events cost a
-    // sub-sweep some 20 us -- read by dist_gibbs_phase_stats
-    static constexpr int kPhases = 5;
-    int phase_timing = 0;
-    double phase_ms[kPhases] = {0, 0, 0, 0, 0};
-    uint64_t phase_batches = 0;
-    std::vector<std::vector<hipEvent_t>> phase_pending;
-    void phase_mark(int i) {
-        if (!phase_timing) return;
-        if (i == 0) phase_pending.emplace_back();
-        if (phase_pending.empty() || (int)phase_pending.back().size() != i)
-            return;   // (a path without all the marks: dropped below)
-        hipEvent_t e = comm_event();
-        HIP_CHECK(hipEventRecord(e, stream()));
-        phase_pending.back().push_back(e);
-    }
-    // (call with the stream drained)
-    void collect_comm_timing() {
-        for (auto & ev : phase_pending) {
-            if ((int)ev.size() == kPhases + 1) {
-                bool ok = true;
-                float ms[kPhases];
-                for (int i = 0; i < kPhases; ++i)
-                    ok = ok && hipEventElapsedTime(&ms[i], ev[i], ev[i + 1])
-                                   == hipSuccess;
-                if (ok) {
-                    for (int i = 0; i < kPhases; ++i) phase_ms[i] += ms[i];
-                    phase_batches += 1;
+        // the phases opt.phase_timing puts between events (tables |
+        // score+sample | handed-over rows | statistics | group set + caches)
+        static constexpr int kPhases = 5;
+        double phase_ms[kPhases] = {0, 0, 0, 0, 0};
+        uint64_t phase_batches = 0;
+        std::vector<std::vector<Event>> phase_pending;
+        // (call with the stream drained)
+        void collect_comm_timing() {
+            for (auto & ev : phase_pending) {
+                if ((int)ev.size() == kPhases + 1) {
+                    bool ok = true;
+                    float ms[kPhases];
+                    for (int i = 0; i < kPhases; ++i)
+                        ok = ok
+                             && hipEventElapsedTime(&ms[i], ev[i].e,
+                                                    ev[i + 1].e) == hipSuccess;
+                    if (ok) {
+                        for (int i = 0; i < kPhases; ++i) phase_ms[i] += ms[i];
+                        phase_batches += 1;
+                    }
                 }
+                for (Event & e : ev) comm_ev_free.push_back(std::move(e));
             }
-            for (hipEvent_t e : ev) comm_ev_free.push_back(e);
-        }
-        phase_pending.clear();
-        for (auto & pr : comm_ev_pending) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) {
-                comm_ms += ms;
-                comm_launches += 1;
+            phase_pending.clear();
+            for (auto & pr : comm_ev_pending) {
+                float ms = 0.f;
+                if (hipEventElapsedTime(&ms, pr.first.e, pr.second.e)
+                    == hipSuccess) {
+                    comm_ms += ms;
+                    comm_launches += 1;
+                }
+                comm_ev_free.push_back(std::move(pr.first));
+                comm_ev_free.push_back(std::move(pr.second));
             }
-            comm_ev_free.push_back(pr.first);
-            comm_ev_free.push_back(pr.second);
+            comm_ev_pending.clear();
         }
-        comm_ev_pending.clear();
+    };
+    Timing tm;
+    // (a member of Gibbs, not of Timing: the option decides)
+    void phase_mark(int i) {
+        if (!opt.phase_timing) return;
+        if (i == 0) tm.phase_pending.emplace_back();
+        if (tm.phase_pending.empty()
+            || (int)tm.phase_pending.back().size() != i)
+            return;   // (a path without all the marks: dropped on collection)
+        Event e = tm.comm_event();
+        HIP_CHECK(hipEventRecord(e.e, stream()));
+        tm.phase_pending.back().push_back(std::move(e));
     }
-
     Gibbs(float alpha_, float d_, int F, const dist_shared_t * shareds)
         : alpha(alpha_), d(d_) {
         ensure_device_ready();
@@ -1557,27 +1711,14 @@ struct Gibbs {
                      "expected alpha > 0, 0 <= d < 1");
         for (int f = 0; f < F; ++f)
             feats.emplace_back(new Slave(shareds[f]));
-        HIP_CHECK(hipEventCreate(&ev0));
-        HIP_CHECK(hipEventCreate(&ev1));
+        tm.use_own_pair();
     }
+    // Every buffer and event is a member that frees itself.  What is left to
+    // do by hand: a copy of the device's state still on its way to
+    // run.pinned_state must land before that buffer goes (members are destroyed
+    // after this body).
     ~Gibbs() {
-        if (publish_ev) (void)hipEventDestroy(publish_ev);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
-        for (hipEvent_t e : comm_ev_free) (void)hipEventDestroy(e);
-        for (auto & pr : comm_ev_pending) {
-            (void)hipEventDestroy(pr.first);
-            (void)hipEventDestroy(pr.second);
-        }
-        if (peek_pending) (void)hipEventSynchronize(peek_event);
-        if (peek_event) (void)hipEventDestroy(peek_event);
-        if (pinned_draw) (void)hipHostFree(pinned_draw);
-        if (pinned_state) (void)hipHostFree(pinned_state);
-        if (pinned_counts) (void)hipHostFree(pinned_counts);
-        if (pinned_seq) (void)hipHostFree(pinned_seq);
-        if (pinned_pairs) (void)hipHostFree(pinned_pairs);
-        if (comm_fault) (void)hipHostFree(comm_fault);
+        if (run.peek_pending) (void)hipEventSynchronize(run.peek_event.e);
     }
 
     int F() const { return (int)feats.size(); }
@@ -1640,7 +1781,7 @@ struct Gibbs {
         ensure_pow_tables(r1 - r0);
         P.pow_lo = pow_lo.p;
         P.pow_hi = pow_hi.p;
-        P.dev = async_active ? dev_ptr() : nullptr;
+        P.dev = run.async_active ? run.dev_ptr() : nullptr;
         return P;
     }
 
@@ -1875,7 +2016,7 @@ struct Gibbs {
     Slave::GridWork hyper_work;
     uint64_t hyper_calls = 0;
     DeviceBuf<float> hyper_scores;
-    HyperDraw * pinned_draw = nullptr;
+    PinnedBuf<HyperDraw> pinned_draw;
 
     Slave & hyper_feature(int f, const char * what) const {
         DIST_REQUIRE(f >= 0 && f < F(),
@@ -1884,7 +2025,7 @@ struct Gibbs {
     }
     void hyper_enter(const char * what, bool reads_cells) {
         DIST_REQUIRE(!batch_open, std::string(what) + ": a batch is open");
-        if (reads_cells) require_whole(what);
+        if (reads_cells) ex.require_whole(what);
         hyper_calls += 1;
     }
     static void check_clustering(float alpha_, float d_) {
@@ -1997,16 +2138,16 @@ struct Gibbs {
     }
     // sample_from_scores_overwrite over hyper_scores[0..n): one engine step
     size_t hyper_draw(size_t n, uint32_t * rng_state) {
-        if (!pinned_draw)
-            HIP_CHECK(hipHostMalloc((void **)&pinned_draw, sizeof(HyperDraw),
-                                    hipHostMallocDefault));
-        pinned_draw->index = ~0u;
-        LAUNCH1(k_hyper_draw, hyper_scores.p, (int)n, *rng_state, pinned_draw);
+        if (!pinned_draw.p) pinned_draw.alloc(1, hipHostMallocDefault);
+        pinned_draw.p->index = ~0u;
+        LAUNCH1(k_hyper_draw, hyper_scores.p, (int)n, *rng_state,
+                pinned_draw.p);
         hyper_work.launches += 1;
         sync();
-        DIST_REQUIRE(pinned_draw->index < n, "internal: the draw did not land");
-        *rng_state = pinned_draw->rng_state;
-        return (size_t)pinned_draw->index;
+        DIST_REQUIRE(pinned_draw.p->index < n,
+                     "internal: the draw did not land");
+        *rng_state = pinned_draw.p->rng_state;
+        return (size_t)pinned_draw.p->index;
     }
     void sample_hypers(int f, const dist_shared_t * shareds, size_t n,
                        uint32_t * rng_state, size_t * chosen) {
@@ -2050,37 +2191,32 @@ struct Gibbs {
     size_t early_n = 0;
     uint64_t batch_serial = 0, early_serial = 0;   // (which batch it is of)
     unsigned launch_publish(size_t n) {
-        if (n > pinned_cap) {
+        if (n > pinned_counts.cap) {
             sync();   // (an earlier publish may still write the old buffer)
-            if (pinned_counts) (void)hipHostFree(pinned_counts);
-            pinned_cap = grow_capacity(n);
-            HIP_CHECK(hipHostMalloc((void **)&pinned_counts,
-                                    pinned_cap * sizeof(int),
-                                    hipHostMallocCoherent));
+            pinned_counts.reserve(n, hipHostMallocCoherent);
         }
-        if (!pinned_seq) {
-            HIP_CHECK(hipHostMalloc((void **)&pinned_seq, sizeof(unsigned),
-                                    hipHostMallocCoherent));
-            *pinned_seq = 0;
+        if (!pinned_seq.p) {
+            pinned_seq.alloc(1, hipHostMallocCoherent);
+            *pinned_seq.p = 0;
         }
         const unsigned ticket = ++publish_ticket;
         hipLaunchKernelGGL(k_publish_counts, dim3(1), dim3(1024), 0, stream(),
-                           py.d_counts.p, (int)n, pinned_counts,
-                           (volatile unsigned *)pinned_seq, ticket);
+                           py.d_counts.p, (int)n, pinned_counts.p,
+                           (volatile unsigned *)pinned_seq.p, ticket);
         HIP_CHECK(hipGetLastError());
         // (what a waiter that has spun long enough sleeps on: THIS kernel,
         // not the stream -- the replay queued behind it is not its business)
-        if (!publish_ev)
-            HIP_CHECK(hipEventCreateWithFlags(
-                &publish_ev, hipEventDisableTiming | hipEventBlockingSync));
-        HIP_CHECK(hipEventRecord(publish_ev, stream()));
+        HIP_CHECK(hipEventRecord(
+            publish_ev.get(hipEventDisableTiming | hipEventBlockingSync),
+            stream()));
         return ticket;
     }
-    hipEvent_t publish_ev = nullptr;
+    Event publish_ev;
     void publish_counts_early() {
         // (k_vs_reduce publishes the sizes of a value-sorted batch itself;
         // an open device-normalised run never asks)
-        if (async_active || (pairs_ticket != 0 && pairs_ticket == publish_ticket))
+        if (run.async_active
+            || (pairs_ticket != 0 && pairs_ticket == publish_ticket))
             return;
         early_n = (size_t)K();
         early_serial = batch_serial;
@@ -2088,19 +2224,13 @@ struct Gibbs {
     }
     void refresh_host_counts() {
         const size_t n = (size_t)K();
-        if (n > pinned_cap) {
-            if (pinned_counts) (void)hipHostFree(pinned_counts);
-            pinned_cap = grow_capacity(n);
-            HIP_CHECK(hipHostMalloc((void **)&pinned_counts,
-                                    pinned_cap * sizeof(int),
-                                    hipHostMallocCoherent));
-        }
+        pinned_counts.reserve(n, hipHostMallocCoherent);
         py.counts.resize(n);
         if (pairs_ticket != 0 && pairs_ticket == publish_ticket) {
             // k_vs_reduce is publishing them: wait for the ticket in every slot
             const unsigned long long want = pairs_ticket;
             pairs_ticket = 0;
-            const volatile unsigned long long * pairs = pinned_pairs;
+            const volatile unsigned long long * pairs = pinned_pairs.p;
             bool seen = false;
             size_t k = 0;
             auto scan = [&] {
@@ -2145,7 +2275,7 @@ struct Gibbs {
         const auto t_poll = std::chrono::steady_clock::now();
         while (!seen) {
             for (int spin = 0; spin < 256 && !seen; ++spin)
-                seen = *(volatile unsigned *)pinned_seq == ticket;
+                seen = *(volatile unsigned *)pinned_seq.p == ticket;
             if (std::chrono::steady_clock::now() - t_poll
                 > std::chrono::microseconds(200))
                 break;
@@ -2154,12 +2284,12 @@ struct Gibbs {
         // surfaces the error of a failed kernel -- that one never writes the
         // ticket)
         if (!seen) {
-            HIP_CHECK(hipEventSynchronize(publish_ev));
-            DIST_REQUIRE(*(volatile unsigned *)pinned_seq == ticket,
+            HIP_CHECK(hipEventSynchronize(publish_ev.e));
+            DIST_REQUIRE(*(volatile unsigned *)pinned_seq.p == ticket,
                          "group sizes were not published");
         }
         std::atomic_thread_fence(std::memory_order_acquire);
-        std::copy(pinned_counts, pinned_counts + n, py.counts.begin());
+        std::copy(pinned_counts.p, pinned_counts.p + n, py.counts.begin());
     }
 
     void load(size_t n, const uint32_t * const * vals, bool vals_on_device,
@@ -2215,8 +2345,8 @@ struct Gibbs {
         // largest value of each discrete feature (validation; sizes the
         // value tables of the count-valued ones)
         max_value.assign((size_t)F(), 0);
-        resume_bound = resume_left = 0;
-        value_partitioned = cells_partial = false;
+        run.resume_bound = run.resume_left = 0;
+        ex.value_partitioned = ex.cells_partial = false;
         vs_cache.clear();
         vs_ranges.clear();
         vs_last = 0;
@@ -2346,7 +2476,7 @@ struct Gibbs {
                              size_t n) {
         RowsArgs A;
         memset(&A, 0, sizeof(A));
-        A.pad = rows_prio_mode;   // (wave priorities by pass)
+        A.pad = opt.rows_prio_mode;   // (wave priorities by pass)
         GtabSource src;
         memset(&src, 0, sizeof(src));
         int n_ops = 0;
@@ -2391,8 +2521,9 @@ struct Gibbs {
         // behind the last: whole blocks are scored, the surplus is masked)
         const int Kpad = (K() + kRowsSuper - 1) / kRowsSuper * kRowsSuper
                          + kRowsSuper;
-        if (rows_fold_mode == 2 || (rows_fold_mode == 1 && n >= 8192)) {
-            const size_t per_code = rows_fold_mode == 2 ? 1 : kFoldRowsPerCode;
+        if (opt.rows_fold_mode == 2 || (opt.rows_fold_mode == 1 && n >= 8192)) {
+            const size_t per_code =
+                opt.rows_fold_mode == 2 ? 1 : Options::kFoldRowsPerCode;
             for (int o = 0; o < n_ops; ++o) {
                 const RowsOp & r = A.op[o];
                 if (r.type == ROP_NICH) break;
@@ -2448,11 +2579,11 @@ struct Gibbs {
         }
         const int W = next;
         if (W > kRowsMaxW) return false;
-        const bool lds_log = nich && rows_scratch_lds_log != 0;
+        const bool lds_log = nich && opt.rows_scratch_lds_log != 0;
         // the exact loops, or scan sampling (tolerance-level, option
         // "sampling")
-        const bool scan = sampling_mode == 1;
-        const int block = rows_scratch_block;
+        const bool scan = opt.sampling_mode == 1;
+        const int block = opt.rows_scratch_block;
         // the program's shape at compile time where an instance exists
         if (n_ops > 4) shape = 0;
         const void * fn = nullptr;
@@ -2576,10 +2707,10 @@ struct Gibbs {
         deferred.reserve(std::max<size_t>(n, 1), 0);
         deferred_count.reserve(1, 0);
         HIP_CHECK(hipMemsetAsync(deferred_count.p, 0, 4, stream()));
-        mark(ev0);
+        tm.mark(tm.ev0);
         LAUNCH(k_row_prepass, n, P, prog, own_score.p, deferred.p,
                deferred_count.p);
-        if ((rows_scratch_mode == 0 && sampling_mode == 0)
+        if ((opt.rows_scratch_mode == 0 && opt.sampling_mode == 0)
             || !launch_rows_scratch(P, prog, n)) {
             const unsigned blocks = (unsigned)std::min<size_t>(
                 (n + kBlock - 1) / kBlock, 256 * 16);
@@ -2599,7 +2730,7 @@ struct Gibbs {
             DeferredLaunch D{&Q};
             dispatch(D);
         }
-        mark(ev1);
+        tm.mark(tm.ev1);
         return true;
     }
     struct SampleLaunch {
@@ -2611,11 +2742,11 @@ struct Gibbs {
             // >> 256 workgroups to fill 256 CUs; grid-stride beyond that
             const unsigned blocks = (unsigned)std::min<size_t>(
                 (n + kBlock - 1) / kBlock, 256 * 16);
-            self->mark(self->ev0);
+            self->tm.mark(self->tm.ev0);
             hipLaunchKernelGGL((k_sweep_sample<A, B, NF>), dim3(blocks),
                                dim3(kBlock), 0, stream(), *P);
             HIP_CHECK(hipGetLastError());
-            self->mark(self->ev1);
+            self->tm.mark(self->tm.ev1);
         }
     };
     struct RowScoreLaunch {
@@ -2640,16 +2771,16 @@ struct Gibbs {
         return sh.dim;
     }
     bool use_value_sorted(size_t rows) const {
-        if (value_sorted_mode == 0 || F() != 1) return false;
+        if (opt.value_sorted_mode == 0 || F() != 1) return false;
         const int kind = feats[0]->sh.kind;
         if (kind != DIST_DD && kind != DIST_DPD && kind != DIST_BB
             && kind != DIST_GP && kind != DIST_BNB)
             return false;
-        if (value_sorted_mode == 2) return true;
+        if (opt.value_sorted_mode == 2) return true;
         // (a value-partitioned rank meets only ITS values: what counts is
         // the rows per value that is there, not per value of the domain)
-        const size_t nv = value_partitioned && present_values
-                              ? std::min<size_t>(present_values, vs_nvals())
+        const size_t nv = ex.value_partitioned && ex.present_values
+                              ? std::min<size_t>(ex.present_values, vs_nvals())
                               : (size_t)vs_nvals();
         return rows >= (size_t)16 * nv && rows >= 4096;
     }
@@ -2708,7 +2839,7 @@ struct Gibbs {
         // spare lane keeps a full tile from handing a row over)
         if (use_stream(*c)) cut_tiles(64 * kVsR - kVsR);
         std::vector<VsTile> narrow;
-        if (c->n_tiles < kVsNarrowBelowTiles || narrow_mode == 2) {
+        if (c->n_tiles < Options::kVsNarrowBelowTiles || opt.narrow_mode == 2) {
             for (uint32_t x = 0; x < nv; ++x)
                 for (uint32_t off = 0; off < h[x]; off += 64)
                     narrow.push_back(VsTile{x, start[x] + off,
@@ -2857,7 +2988,7 @@ struct Gibbs {
             self->phase_mark(1);
             {
                 HOST_PROBE(10, "      mark(ev0)");
-                self->mark(self->ev0);
+                self->tm.mark(self->tm.ev0);
             }
             HOST_PROBE(11, "      sample launch+mark");
             // a launch that cannot fill the chip spreads out: a wave per
@@ -2874,15 +3005,15 @@ struct Gibbs {
                         c->sorted_rows.p, D);
                 };
                 const bool whole =
-                    self->narrow_read_ahead
-                        ? self->narrow_read_ahead == 8
+                    self->opt.narrow_read_ahead
+                        ? self->opt.narrow_read_ahead == 8
                         : c->n_narrow_tiles <= 8u * (uint32_t)self->cu_count();
                 if (whole)
                     launch(std::integral_constant<int, 8>());
                 else
                     launch(std::integral_constant<int, 4>());
                 HIP_CHECK(hipGetLastError());
-                self->mark(self->ev1);
+                self->tm.mark(self->tm.ev1);
                 return;
             }
             const bool small = !T.band_mode && c->n_tiles < 4096;
@@ -2902,7 +3033,7 @@ struct Gibbs {
                                    stream(), *P, T, c->tiles.p, c->n_tiles,
                                    band_ids, c->sorted_rows.p, D);
             HIP_CHECK(hipGetLastError());
-            self->mark(self->ev1);
+            self->tm.mark(self->tm.ev1);
         }
     };
     // May this batch of the open device-normalised run take the fused launch
@@ -2911,7 +3042,8 @@ struct Gibbs {
     // matrix (its sort buffers are the handed-over rows' strips, and
     // k_vs_reduce writes what the fused launch reads).
     bool fused_ok(const VsCache & c, int Kpad) const {
-        if (!fused_tables_mode || !async_active || sampling_mode != 0)
+        if (!opt.fused_tables_mode || !run.async_active
+            || opt.sampling_mode != 0)
             return false;
         if (Kpad > kTablesMaxK || c.mixed_chunks || any_float_stats())
             return false;
@@ -2936,19 +3068,19 @@ struct Gibbs {
         A.i0_in = f.i0.p;
         A.i1_in = f.i1.p;
         A.counts_in = py.d_counts.p;
-        A.snap_in = snap_counts.p;
-        A.dev_in = dev_ptr();
-        std::swap(f.i0.p, alt_i0.p);   std::swap(f.i0.cap, alt_i0.cap);
-        std::swap(f.i1.p, alt_i1.p);   std::swap(f.i1.cap, alt_i1.cap);
-        std::swap(py.d_counts.p, alt_counts.p);
-        std::swap(py.d_counts.cap, alt_counts.cap);
-        std::swap(snap_counts.p, alt_snap.p);
-        std::swap(snap_counts.cap, alt_snap.cap);
-        dev_cur ^= 1;
+        A.snap_in = run.snap_counts.p;
+        A.dev_in = run.dev_ptr();
+        std::swap(f.i0.p, run.alt_i0.p);   std::swap(f.i0.cap, run.alt_i0.cap);
+        std::swap(f.i1.p, run.alt_i1.p);   std::swap(f.i1.cap, run.alt_i1.cap);
+        std::swap(py.d_counts.p, run.alt_counts.p);
+        std::swap(py.d_counts.cap, run.alt_counts.cap);
+        std::swap(run.snap_counts.p, run.alt_snap.p);
+        std::swap(run.snap_counts.cap, run.alt_snap.cap);
+        run.dev_cur ^= 1;
         A.feat = f.view();
         A.counts_out = py.d_counts.p;
-        A.snap_out = snap_counts.p;
-        A.dev_out = dev_ptr();
+        A.snap_out = run.snap_counts.p;
+        A.dev_out = run.dev_ptr();
         A.shifted = py.d_shifted.p;
         A.base = base.p;
         A.base_single = base_single.p;
@@ -2967,25 +3099,26 @@ struct Gibbs {
         A.k_limit = T.Kuse;
         launch_lds<&k_vs_tables<KIND>>(dim3(T.n_values), dim3(kTablesBlock),
                                        vs_tables_lds(T.Kpad), A, T);
-        finish_pending = false;   // (this launch normalised the group set)
+        run.finish_pending = false;   // (this launch normalised the group set)
         base_valid = true;
         P.feat[0] = f.view();
         P.counts = py.d_counts.p;
-        P.dev = dev_ptr();
+        P.dev = run.dev_ptr();
         fused_batches += 1;
     }
 
     // Tables (k_vs_prepare) pay when several tiles share a value's vector;
     // with a tile or so per value the tile builds the vector itself.
     bool use_stream(const VsCache & c) const {
-        if (value_stream_mode == 0) return false;
-        if (value_stream_mode == 2) return true;
+        if (opt.value_stream_mode == 0) return false;
+        if (opt.value_stream_mode == 2) return true;
         // ... and where the tables are large: small ones are built in a few
         // microseconds and serve every wave from the scalar cache or LDS,
         // while a streaming tile evaluates K scores and exponentials per pass
         // (the group count the run began with: K() is an inflated bound while
         // a device-normalised run is open)
-        const size_t groups = async_active ? (size_t)async_K0 : (size_t)K();
+        const size_t groups =
+            run.async_active ? (size_t)run.async_K0 : (size_t)K();
         if ((size_t)vs_nvals() * groups < ((size_t)1 << 21)) return false;
         return (size_t)c.n_tiles * 2 <= (size_t)c.n_values_present * 3;
     }
@@ -2998,13 +3131,13 @@ struct Gibbs {
             const uint32_t per = kVsStreamBlock / 64;
             hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(1), 0, stream(),
                                self->deferred_count.p, c->n_other);
-            self->mark(self->ev0);
+            self->tm.mark(self->tm.ev0);
             // two rows of K likelihoods per tile (either class's vector)
             // between the total's pass and the scan (up to 2 GiB of scratch; beyond that they are computed
             // again, as before)
             const size_t stride = ((size_t)self->K() + 63) & ~(size_t)63;
             float * scratch = nullptr;
-            if (self->stream_scratch_mode
+            if (self->opt.stream_scratch_mode
                 && (size_t)c->n_tiles * 2 * stride <= ((size_t)1 << 29)) {
                 self->vsScratch.reserve(
                     grow_capacity((size_t)c->n_tiles * 2 * stride), 0);
@@ -3017,9 +3150,9 @@ struct Gibbs {
                                    c->tiles.p, c->n_tiles, c->sorted_rows.p,
                                    self->deferred.p, self->deferred_count.p,
                                    scratch, (uint32_t)stride,
-                                   self->sample_prio_mode);
+                                   self->opt.sample_prio_mode);
             HIP_CHECK(hipGetLastError());
-            self->mark(self->ev1);
+            self->tm.mark(self->tm.ev1);
         }
     };
     void sample_value_stream(SweepParams & P, VsCache & c) {
@@ -3066,7 +3199,7 @@ struct Gibbs {
         template <int KIND>
         void go() {
             const size_t n = P->row_end - P->row_begin;
-            self->mark(self->ev0);
+            self->tm.mark(self->tm.ev0);
             hipLaunchKernelGGL((k_vs_scan_prepare<KIND>), dim3(T.n_values),
                                dim3(kVsScanBlock),
                                vs_scan_prepare_lds(T.Kpad, T.lds_scores != 0),
@@ -3078,7 +3211,7 @@ struct Gibbs {
                                c->sorted_rows.p, n, self->deferred.p,
                                self->deferred_count.p);
             HIP_CHECK(hipGetLastError());
-            self->mark(self->ev1);
+            self->tm.mark(self->tm.ev1);
         }
     };
     uint64_t scan_batches = 0;
@@ -3126,13 +3259,13 @@ struct Gibbs {
         phase_mark(0);
         const int Kpad = (K() + kVsUnroll - 1) / kVsUnroll * kVsUnroll;
         batch_k_limit = k_limit();
-        const bool fused = sampling_mode != 1 && !use_stream(c)
+        const bool fused = opt.sampling_mode != 1 && !use_stream(c)
                            && fused_ok(c, Kpad);
         batch_fused = fused;
         // the last batch left its group set to a fused launch: any other
         // path wants it normalised and the caches rebuilt first
         if (!fused) run_pending_finish();
-        if (sampling_mode == 1) return sample_value_scan(P, c);
+        if (opt.sampling_mode == 1) return sample_value_scan(P, c);
         if (use_stream(c)) return sample_value_stream(P, c);
         const size_t n = P.row_end - P.row_begin;
         const uint32_t nv = (uint32_t)vs_nvals();
@@ -3154,13 +3287,13 @@ struct Gibbs {
         const bool narrow = use_narrow(c, Kuse);
         narrow_batches += narrow ? 1 : 0;
         const bool large = !narrow
-                           && c.n_tiles >= (uint32_t)running_sums_min_tiles;
+                           && c.n_tiles >= (uint32_t)opt.running_sums_min_tiles;
         const bool prefix = large && Kpad <= 8192;
         // ... or, where k_vs_tables runs, the cells' totals in their place:
         // its idle threads fold them while the tiles skip their total pass
         const bool totals =
-            fused && (shared_totals_mode == 2
-                      || (shared_totals_mode == 1 && prefix));
+            fused && (opt.shared_totals_mode == 2
+                      || (opt.shared_totals_mode == 1 && prefix));
         // the arg-max group's rows get a tile of their own per value when the
         // launch is large (and group-sorted: k_vs_apply's LDS sort fits)
         // ... and their workgroups do not push the launch past what is
@@ -3232,7 +3365,7 @@ struct Gibbs {
             T.own = vsOwn.p;
             T.band_by_chunk = 1;
         }
-        T.prio_mode = sample_prio_mode;
+        T.prio_mode = opt.sample_prio_mode;
         if (totals) T.tot = vsTot.p;
         // DIST_VS_STAMPS=<file>: per-wave phase stamps of every launch (the
         // last one stays in the file): tools/vs_stamps.py
@@ -3306,11 +3439,12 @@ struct Gibbs {
             batch_fused = false;
             return;
         }
-        timing_this_batch =
-            kernel_timing > 0 && timing_tick++ % (uint64_t)kernel_timing == 0;
+        tm.timing_this_batch =
+            opt.kernel_timing > 0
+            && tm.timing_tick++ % (uint64_t)opt.kernel_timing == 0;
         // (a host-driven batch: whatever sharded run was closed before it is
         // not taken up again)
-        if (!async_active) resume_bound = resume_left = 0;
+        if (!run.async_active) run.resume_bound = run.resume_left = 0;
         upload_maps();
         SweepParams P;
         {
@@ -3332,14 +3466,14 @@ struct Gibbs {
         } else if (r1 - r0 <= 2048 && wave_rows_fit()) {
             // a handful of rows (the sequential chain is one): a wave each
             prepare(P, false);
-            mark(ev0);
+            tm.mark(tm.ev0);
             WaveRowsLaunch L{&P, K(),
                              (unsigned)((r1 - r0 + kBlock / 64 - 1)
                                         / (kBlock / 64))};
             dispatch(L);
-            mark(ev1);
+            tm.mark(tm.ev1);
             generic_batches += 1;
-        } else if ((uses_runtime_kernel() || (program_all && F() >= 1))
+        } else if ((uses_runtime_kernel() || (opt.program_all && F() >= 1))
                    && sample_by_program(P)) {
             generic_batches += 1;
         } else {
@@ -3348,20 +3482,20 @@ struct Gibbs {
             dispatch(L);
             generic_batches += 1;
         }
-        timing_pending = true;
+        tm.timing_pending = true;
     }
     // the events of the open batch are read once the batch has been drained
     // (batch_finish has synchronised by then): no extra host sync per batch
     void collect_timing() {
-        if (!timing_pending) return;
-        timing_pending = false;
-        if (!timing_this_batch) return;
-        HIP_CHECK(hipEventSynchronize(ev1));
+        if (!tm.timing_pending) return;
+        tm.timing_pending = false;
+        if (!tm.timing_this_batch) return;
+        HIP_CHECK(hipEventSynchronize(tm.ev1));
         float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, ev0, ev1));
-        kernel_ms += ms;
-        kernel_launches += 1;
-        kernel_rows += batch_end - batch_begin;
+        HIP_CHECK(hipEventElapsedTime(&ms, tm.ev0, tm.ev1));
+        tm.kernel_ms += ms;
+        tm.kernel_launches += 1;
+        tm.kernel_rows += batch_end - batch_begin;
         static const bool trace_deferred = getenv("DIST_TRACE_DEFERRED");
         if (batch_value_sorted && trace_deferred) {
             uint32_t n = 0;
@@ -3477,10 +3611,6 @@ struct Gibbs {
         replay_sorted(old_dev, new_dev, 0, n, vals);
         if (reset && !batch_open) rebuild_caches();
     }
-    // "float_stats": 0 the ordered replay (bit-identical to the sequential
-    // chain's running updates; default), 1 merged: binary64 sums per group
-    // (kernels.h, k_merge_float_*; tolerance-level)
-    int float_stats_mode = 0;
     DeviceBuf<double> merge_stage, merge_image;
     uint64_t merged_batches = 0;
     MergeLayout merge_layout() const {
@@ -3500,7 +3630,7 @@ struct Gibbs {
         return L;
     }
     bool merged_floats() const {
-        return float_stats_mode == 1 && any_float_stats()
+        return opt.float_stats_mode == 1 && any_float_stats()
                && merge_float_lds(merge_layout().words) <= kLdsWorkgroupLimit;
     }
     // the open batch's float-statistic sums into merge_image (not applied)
@@ -3599,7 +3729,7 @@ struct Gibbs {
             const int sole = c.one_chunk_per_value ? 1 : 0;
             unsigned long long * pairs = nullptr;
             unsigned pairs_seq = 0;
-            if (stage && img.counts == py.d_counts.p && !async_active) {
+            if (stage && img.counts == py.d_counts.p && !run.async_active) {
                 pairs = pairs_buffer();   // live statistics: publish sizes
                 pairs_seq = pairs_ticket = ++publish_ticket;
             }
@@ -3612,7 +3742,7 @@ struct Gibbs {
             // while the chunk's other waves add up the moves)
             int lds_told = 0;
             size_t lds_sort_used = lds_sort;
-            if (batch_fused && sort && !gp && apply_overlap_mode) {
+            if (batch_fused && sort && !gp && opt.apply_overlap_mode) {
                 lds_sort_used = vs_apply_overlap_lds(k_lds);
                 lds_told = (int)lds_sort_used;
             }
@@ -3647,7 +3777,7 @@ struct Gibbs {
             // other form clears the stamps of a range that has some
             VsOffsets O;
             memset(&O, 0, sizeof(O));
-            if (sort && async_active && c.one_value_chunks) {
+            if (sort && run.async_active && c.one_value_chunks) {
                 if (c.off_stride < K() + 2) {
                     c.off_stride = (int)grow_capacity((size_t)K() + 2);
                     c.grp_off.release();
@@ -3677,7 +3807,8 @@ struct Gibbs {
                                        c.n_chunks, K(),
                                        (uint32_t)vs_nvals(), pairs,
                                        pairs_seq,
-                                       async_active ? dev_ptr() : nullptr,
+                                       run.async_active ? run.dev_ptr()
+                                                        : nullptr,
                                        k_limit(),
                                        batch_fused ? c.multi.p : nullptr,
                                        batch_fused ? c.n_multi : 0u,
@@ -3732,13 +3863,12 @@ struct Gibbs {
     // the general rows' integer statistics: per-group totals through LDS
     // where (1 + 2 F) K integers fit a workgroup's, else direct atomics
     uint64_t staged_applies = 0;
-    int apply_stage_mode = 1;   // 0: never the all-in-LDS form
     void apply_moves(size_t n, const SweepParams & P, const StatImage & img,
                      const uint32_t * p2g, uint32_t * assign_out) {
         // the whole integer image in LDS (small categoricals): no global
         // atomics, the workgroups' images meet in a staging matrix
         const size_t all_words = stat_words();
-        if (apply_stage_mode
+        if (opt.apply_stage_mode
             && apply_moves_stage_lds(all_words) <= kLdsWorkgroupLimit
             && n >= (size_t)4 * K()) {
             bool cat = false;
@@ -3818,28 +3948,23 @@ struct Gibbs {
     // change their own, in place
     StatImage exchange_image(int32_t * words, size_t k) {
         StatImage img = word_image(words, k);
-        if (value_partitioned) img.cnt[0] = feats[0]->cnt.p;
+        if (ex.value_partitioned) img.cnt[0] = feats[0]->cnt.p;
         return img;
     }
     size_t exchange_words(size_t k) const {
-        return value_partitioned ? 3 * k : stat_words(k);
+        return ex.value_partitioned ? 3 * k : stat_words(k);
     }
     void batch_delta_exchange(int32_t * words, size_t k) {
         DIST_REQUIRE(batch_open, "no open batch");
-        if (value_partitioned) cells_partial = true;
+        if (ex.value_partitioned) ex.cells_partial = true;
         if (batch_end == batch_begin) return;
         apply_ints(exchange_image(words, k));
     }
     unsigned long long * pairs_buffer() {
-        if ((size_t)K() > pinned_pairs_cap) {
-            if (pinned_pairs) (void)hipHostFree(pinned_pairs);
-            pinned_pairs_cap = grow_capacity((size_t)K());
-            HIP_CHECK(hipHostMalloc((void **)&pinned_pairs,
-                                    pinned_pairs_cap * 8,
-                                    hipHostMallocCoherent));
-            memset(pinned_pairs, 0, pinned_pairs_cap * 8);
+        if (pinned_pairs.reserve((size_t)K(), hipHostMallocCoherent)) {
+            memset(pinned_pairs.p, 0, pinned_pairs.cap * 8);
         }
-        return pinned_pairs;
+        return pinned_pairs.p;
     }
     // clear = leave the image zeroed behind (it is not const then)
     void batch_apply_delta(int32_t * delta_dev, bool clear = false) {
@@ -3870,7 +3995,7 @@ struct Gibbs {
             if (cells) push(a.cnt[f], k * feats[f]->dim());
         }
         unsigned long long * pairs = nullptr;
-        if (!async_active) {   // the host will want the new group sizes
+        if (!run.async_active) {   // the host will want the new group sizes
             pairs = pairs_buffer();
             pairs_ticket = ++publish_ticket;
         }
@@ -4009,7 +4134,8 @@ struct Gibbs {
     // sub-sweep and 18 % at 65 536; while every sweep pulled the state back it
     // only paid below some 500 000 rows)
     bool async_eligible(size_t r0, size_t r1, size_t batch) const {
-        if (device_normalise_mode == 0 || cluster != 0 || F() != 1) return false;
+        if (opt.device_normalise_mode == 0 || cluster != 0 || F() != 1)
+            return false;
         if (r1 <= r0 || any_float_stats() || py.n_empty < 1) return false;
         const size_t last = (r1 - r0) % batch;
         if (!use_value_sorted(std::min(batch, r1 - r0))) return false;
@@ -4028,10 +4154,10 @@ struct Gibbs {
         N.F = F();
         for (int f = 0; f < F(); ++f) N.feat[f] = feats[f]->view();
         N.counts = py.d_counts.p;
-        N.snap = snap_counts.p;
+        N.snap = run.snap_counts.p;
         N.p2g = d_maps.p;
         N.g2p = reinterpret_cast<int32_t *>(d_maps.p + maps_pcap);
-        N.dev = dev_ptr();
+        N.dev = run.dev_ptr();
         N.n_empty = py.n_empty;
         launch_lds<&k_normalise>(dim3(1), dim3(kNormaliseBlock),
                                  normalise_lds(K()), N);
@@ -4043,14 +4169,14 @@ struct Gibbs {
         if (batch_fused) {
             // the next k_vs_tables normalises the group set and rebuilds the
             // caches on its way (or run_pending_finish, whoever comes first)
-            finish_pending = true;
+            run.finish_pending = true;
             return;
         }
         finish_kernels();
     }
     void run_pending_finish() {
-        if (!finish_pending) return;
-        finish_pending = false;
+        if (!run.finish_pending) return;
+        run.finish_pending = false;
         finish_kernels();
     }
     // k_normalise + k_batch_finish on the state the last batch left
@@ -4080,8 +4206,8 @@ struct Gibbs {
         base_valid = true;
         Q.p2g = d_maps.p;
         Q.g2p = reinterpret_cast<int32_t *>(d_maps.p + maps_pcap);
-        Q.dev = dev_ptr();
-        Q.snap = snap_counts.p;
+        Q.dev = run.dev_ptr();
+        Q.snap = run.snap_counts.p;
         hipLaunchKernelGGL(k_batch_finish,
                            dim3((unsigned)((cells + kBlock - 1) / kBlock),
                                 (unsigned)(F() + 1)),
@@ -4092,14 +4218,14 @@ struct Gibbs {
     void pull_host_state() {
         // the run is queued on the stream of the thread that swept; another
         // thread closing it must drain THAT stream, not its own
-        if (async_stream && async_stream != stream())
-            HIP_CHECK(hipStreamSynchronize(async_stream));
+        if (run.async_stream && run.async_stream != stream())
+            HIP_CHECK(hipStreamSynchronize(run.async_stream));
         run_pending_finish();   // (a fused batch left its group set open)
         sync();
         DevState both[2];
-        dev_state.download(both, 2);
-        const DevState st = both[dev_cur];
-        run_epoch = (uint32_t)st.pad;   // (where the next run goes on)
+        run.dev_state.download(both, 2);
+        const DevState st = both[run.dev_cur];
+        run.run_epoch = (uint32_t)st.pad;   // (where the next run goes on)
         const size_t Kn = (size_t)st.K;
         py.counts.resize(Kn);
         py.d_counts.download(py.counts.data(), Kn);
@@ -4121,104 +4247,57 @@ struct Gibbs {
     // Everything a device-normalised run of `n_batches` batches may grow
     // into is reserved up front (growing a buffer synchronises), the state
     // the kernels read is put on the device, and K() becomes the bound.
-    hipEvent_t async_own0 = nullptr, async_own1 = nullptr;
-    std::vector<size_t> async_rows;   // rows of each TIMED batch of the run
-    // A run stays open when its sweep returns (the host's mirrors are pulled
-    // by the next call that is not another such sweep: settle()), so that
-    // consecutive sweeps pay for the hand-over of the state once: room for
-    // kAsyncSweeps sweeps like the first is reserved where the kernels' LDS
-    // allows, and async_left counts the batches still covered.
-    static constexpr size_t kAsyncSweeps = 8;
-    // ... and with the fused launch (whose work follows the per-launch bound
-    // on the group count, k_limit(), not the run's) as many sweeps as its
-    // LDS allows, up to this many batches
-    static constexpr size_t kAsyncMaxBatches = 16384;
-    // The group count is at most this when batch `index` of the open run is
-    // sampled: every batch can fill each empty group once.  K_seen is the
-    // device's own count, copied back without waiting for it (async_peek).
-    size_t run_batches = 0;          // batches sampled in the open run
-    int K_seen = 0;
-    size_t K_seen_batch = 0;
     int batch_k_limit = 0;           // k_limit() when the open batch was sampled
-    DevState * pinned_state = nullptr;
-    hipEvent_t peek_event = nullptr;
-    bool peek_pending = false;
-    size_t peek_batch = 0;
+    // the group count is at most this when the next batch of the open run is
+    // sampled (Run::K_seen)
     int k_limit() const {
-        if (!async_active) return K();
-        const size_t grown = (size_t)K_seen
-            + (run_batches - K_seen_batch + 1) * (size_t)py.n_empty;
+        if (!run.async_active) return K();
+        const size_t grown = (size_t)run.K_seen
+            + (run.run_batches - run.K_seen_batch + 1) * (size_t)py.n_empty;
         return (int)std::min<size_t>((size_t)K(), grown);
     }
     // the device's state on its way to pinned memory (no wait); the next
     // sweep of the run picks it up if it has arrived
     void async_peek() {
-        if (!pinned_state) {
-            HIP_CHECK(hipHostMalloc((void **)&pinned_state, sizeof(DevState),
-                                    hipHostMallocDefault));
-            HIP_CHECK(hipEventCreateWithFlags(&peek_event,
-                                              hipEventDisableTiming));
+        if (!run.pinned_state.p) {
+            run.pinned_state.alloc(1, hipHostMallocDefault);
+            run.peek_event.get(hipEventDisableTiming);
         }
-        if (peek_pending) return;   // (one in flight)
-        HIP_CHECK(hipMemcpyAsync(pinned_state, dev_ptr(), sizeof(DevState),
-                                 hipMemcpyDeviceToHost, stream()));
-        HIP_CHECK(hipEventRecord(peek_event, stream()));
-        peek_pending = true;
-        peek_batch = run_batches;
+        if (run.peek_pending) return;   // (one in flight)
+        HIP_CHECK(hipMemcpyAsync(run.pinned_state.p, run.dev_ptr(),
+                                 sizeof(DevState), hipMemcpyDeviceToHost,
+                                 stream()));
+        HIP_CHECK(hipEventRecord(run.peek_event.e, stream()));
+        run.peek_pending = true;
+        run.peek_batch = run.run_batches;
     }
     void async_peek_collect() {
-        if (!peek_pending || hipEventQuery(peek_event) != hipSuccess) return;
-        peek_pending = false;
+        if (!run.peek_pending
+            || hipEventQuery(run.peek_event.e) != hipSuccess)
+            return;
+        run.peek_pending = false;
         // (the state before the last batch's own moves were normalised)
-        K_seen = pinned_state->K + py.n_empty;
-        K_seen_batch = peek_batch;
+        run.K_seen = run.pinned_state.p->K + py.n_empty;
+        run.K_seen_batch = run.peek_batch;
     }
-    size_t async_left = 0;
-    int async_K0 = 0;                    // the group count the run began with
-    hipStream_t async_stream = nullptr;  // the stream the run is queued on
-    // a sharded run (dist_gibbs_sweep_sharded) goes on only with the tiling
-    // all ranks agreed on when it was opened
-    size_t sharded_batches = 0, sharded_batch_rows = 0;
-    // A sharded run this rank closed ITSELF between two passes (any look at
-    // the state does: settle) can be taken up again with the bound on the
-    // group count and the batches it had left -- to its peers, who kept
-    // theirs open, it then looks like a run that went on: the same collectives
-    // of the same size (stat_words() follows the bound), and the same results
-    // (closing a run never changes one).  So whether open runs go on needs
-    // no word between the ranks, and no pass begins with a host round trip.
-    size_t resume_bound = 0, resume_left = 0;   // 0: nothing to take up
-    // What the ranks exchange per sub-sweep is sized by the LIVE part of the
-    // group set, not by the run's bound (round 5 sent the bound's image: 8.4
-    // MB where 1.1 MB were in use): a batch's deltas touch the groups that
-    // existed when it was sampled, and every batch can fill each empty group
-    // once, so batch j of a run that began with K0 groups touches slots below
-    // K0 + j * n_empty -- a number every rank knows without asking (the
-    // device's own count, K_seen, arrives asynchronously and is not).  A rank
-    // that closed its run and takes it up again keeps the origin it shared
-    // with its peers.
-    size_t run_origin_K0 = 0, run_origin_done = 0;
-    size_t resume_K0 = 0, resume_done = 0;
-    uint64_t sharded_run_serial = 0;   // runs the ranks agreed to open
+    // the groups a batch's deltas can touch (Run::run_origin_K0)
     size_t exchange_K() const {
-        if (!async_active) return (size_t)K();
-        return std::min<size_t>((size_t)K(), run_origin_K0
-                                + run_origin_done * (size_t)py.n_empty);
+        if (!run.async_active) return (size_t)K();
+        return std::min<size_t>((size_t)K(), run.run_origin_K0
+                                + run.run_origin_done * (size_t)py.n_empty);
     }
-    void forget_resume() { resume_bound = resume_left = 0; }
     // the exchange's header did not add up (k_add_words, CommCheck): some
     // rank's run stood elsewhere, the sums applied since are not to be trusted
     void check_comm_fault() {
-        if (!comm_fault || *comm_fault == 0) return;
-        const unsigned at = *comm_fault & 0x7FFFFFFFu;
-        *comm_fault = 0;
+        if (!ex.comm_fault.p || *ex.comm_fault.p == 0) return;
+        const unsigned at = *ex.comm_fault.p & 0x7FFFFFFFu;
+        *ex.comm_fault.p = 0;
         poisoned = true;
         throw Error("ERROR ranks diverged: the header of exchange #"
                     + std::to_string(at) + " did not add up -- a rank changed "
                     "its engine between two passes of dist_gibbs_sweep_sharded "
                     "(or passes a different tiling); the statistics are lost");
     }
-    uint64_t resumed_runs = 0;
-    DeviceBuf<int> agree_flag;
     // Is [r0, r1) a range whose batches the fused launch takes, as far as
     // that is known before a run is open?  (ADVICE: a long run sizes every
     // OTHER path by its inflated bound on the group count -- k_vs_prepare's
@@ -4226,7 +4305,8 @@ struct Gibbs {
     // where the first range has been seen to take the fused launch: a range
     // that was never sorted yet, i.e. a first sweep, gets a short run.)
     bool vs_expect_fused(size_t r0, size_t r1) const {
-        if (!fused_tables_mode || sampling_mode != 0 || any_float_stats())
+        if (!opt.fused_tables_mode || opt.sampling_mode != 0
+            || any_float_stats())
             return false;
         for (size_t i = 0; i < vs_ranges.size(); ++i) {
             if (vs_ranges[i].first != r0 || vs_ranges[i].second != r1) continue;
@@ -4239,51 +4319,50 @@ struct Gibbs {
         }
         return false;
     }
-    int async_bound_K = 0;   // the open run's bound on the group count
-    int run_batches_cap = 0; // debug.run_batches_cap (0: none)
     void async_begin(size_t n_first, bool expect_fused = true,
                      size_t forced_bound = 0, size_t forced_left = 0) {
         const int K0 = K();
         const size_t ne = (size_t)py.n_empty;
-        size_t n_batches = kAsyncSweeps * n_first;
+        size_t n_batches = Run::kAsyncSweeps * n_first;
         // (only where the fused launch will run: every other path sizes its
         // work by the run's bound -- the scan mode's prefix tables, for one)
-        if (expect_fused && fused_tables_mode && sampling_mode == 0
+        if (expect_fused && opt.fused_tables_mode && opt.sampling_mode == 0
             && (size_t)K0 + n_first * ne + 64 <= kTablesMaxK) {
             const size_t room = ((size_t)kTablesMaxK - 64 - (size_t)K0) / ne;
             const size_t sweeps =
-                std::min(room, kAsyncMaxBatches) / std::max<size_t>(n_first, 1);
+                std::min(room, Run::kAsyncMaxBatches)
+                / std::max<size_t>(n_first, 1);
             n_batches = std::max<size_t>(sweeps, 1) * n_first;
         }
         if (!async_bound_fits((size_t)K0 + n_batches * ne)
-            || n_batches > kAsyncMaxBatches)
+            || n_batches > Run::kAsyncMaxBatches)
             n_batches = n_first;
         // (debug.run_batches_cap: short runs, so that a test sees one used up)
-        if (run_batches_cap && n_first)
+        if (opt.run_batches_cap && n_first)
             n_batches = std::min(n_batches, std::max<size_t>(
-                n_first, (size_t)run_batches_cap / n_first * n_first));
+                n_first, (size_t)opt.run_batches_cap / n_first * n_first));
         if (forced_bound) n_batches = forced_left;   // (a run taken up again)
-        async_left = n_batches;
-        run_batches = 0;
-        K_seen = K0;
-        K_seen_batch = 0;
-        if (peek_pending) {   // (a copy of another run's state: not wanted)
-            (void)hipEventSynchronize(peek_event);
-            peek_pending = false;
+        run.async_left = n_batches;
+        run.run_batches = 0;
+        run.K_seen = K0;
+        run.K_seen_batch = 0;
+        if (run.peek_pending) {   // (a copy of another run's state: not wanted)
+            (void)hipEventSynchronize(run.peek_event.e);
+            run.peek_pending = false;
         }
         const int bound = forced_bound ? (int)forced_bound
                                        : K0 + (int)n_batches * py.n_empty;
         DIST_REQUIRE((size_t)K0 + n_batches * ne <= (size_t)bound,
                      "internal: a run's bound below what its batches can grow");
-        async_bound_K = bound;
+        run.async_bound_K = bound;
         if (forced_bound) {   // (taken up again: the peers' origin)
-            run_origin_K0 = resume_K0;
-            run_origin_done = resume_done;
+            run.run_origin_K0 = run.resume_K0;
+            run.run_origin_done = run.resume_done;
         } else {
-            run_origin_K0 = (size_t)K0;
-            run_origin_done = 0;
+            run.run_origin_K0 = (size_t)K0;
+            run.run_origin_done = 0;
         }
-        resume_bound = resume_left = 0;
+        run.resume_bound = run.resume_left = 0;
         py.reserve(bound);
         for (auto & s : feats) s->reserve(bound);
         if ((size_t)bound > base.cap || (size_t)bound > base_single.cap) {
@@ -4302,10 +4381,10 @@ struct Gibbs {
         st.nonempty = K0 - py.n_empty;
         // (DevState::pad: the removal epoch the groups' recorded offsets are
         // stamped with, VsOffsets; it moves on once per batch at most)
-        if (tracker.repacked != repacked_seen || run_epoch == 0u)
-            run_epoch = (run_epoch + (1u << 20)) & ~((1u << 20) - 1u);
-        repacked_seen = tracker.repacked;
-        if (run_epoch == 0u) {   // wrapped: no old stamp may match again
+        if (tracker.repacked != run.repacked_seen || run.run_epoch == 0u)
+            run.run_epoch = (run.run_epoch + (1u << 20)) & ~((1u << 20) - 1u);
+        run.repacked_seen = tracker.repacked;
+        if (run.run_epoch == 0u) {   // wrapped: no old stamp may match again
             for (auto & c : vs_cache)
                 if (c->off_epoch.p)
                     HIP_CHECK(hipMemsetAsync(c->off_epoch.p, 0,
@@ -4315,29 +4394,32 @@ struct Gibbs {
             if (remap_log.p)
                 HIP_CHECK(hipMemsetAsync(remap_log.p, 0, remap_log.cap * 4,
                                          stream()));
-            run_epoch = 1u << 20;
+            run.run_epoch = 1u << 20;
         }
-        st.pad = (int)run_epoch;
+        st.pad = (int)run.run_epoch;
         const DevState both[2] = {st, st};
-        dev_state.upload(both, 2);
-        dev_cur = 0;
-        finish_pending = false;
-        snap_counts.reserve(grow_capacity((size_t)bound), 0);
-        HIP_CHECK(hipMemcpyAsync(snap_counts.p, py.d_counts.p,
+        run.dev_state.upload(both, 2);
+        run.dev_cur = 0;
+        run.finish_pending = false;
+        run.snap_counts.reserve(grow_capacity((size_t)bound), 0);
+        HIP_CHECK(hipMemcpyAsync(run.snap_counts.p, py.d_counts.p,
                                  (size_t)K0 * 4, hipMemcpyDeviceToDevice,
                                  stream()));
         // the other set of per-group buffers (k_vs_tables): as large as the
         // live ones, whichever way round they are swapped by now
-        alt_counts.reserve(std::max(py.d_counts.cap, alt_counts.cap), 0);
-        py.d_counts.reserve(alt_counts.cap, (size_t)K0);
-        alt_snap.reserve(std::max(snap_counts.cap, alt_snap.cap), 0);
-        snap_counts.reserve(alt_snap.cap, (size_t)K0);
+        run.alt_counts.reserve(
+            std::max(py.d_counts.cap, run.alt_counts.cap), 0);
+        py.d_counts.reserve(run.alt_counts.cap, (size_t)K0);
+        run.alt_snap.reserve(
+            std::max(run.snap_counts.cap, run.alt_snap.cap), 0);
+        run.snap_counts.reserve(run.alt_snap.cap, (size_t)K0);
         if (F() == 1) {
             Slave & f = *feats[0];
             const size_t cap = std::max<size_t>(
-                {f.i0.cap, f.i1.cap, alt_i0.cap, alt_i1.cap, (size_t)f.cap});
-            alt_i0.reserve(cap, 0);
-            alt_i1.reserve(cap, 0);
+                {f.i0.cap, f.i1.cap, run.alt_i0.cap, run.alt_i1.cap,
+                 (size_t)f.cap});
+            run.alt_i0.reserve(cap, 0);
+            run.alt_i1.reserve(cap, 0);
             f.i0.reserve(cap, (size_t)K0);
             f.i1.reserve(cap, (size_t)K0);
         }
@@ -4345,90 +4427,72 @@ struct Gibbs {
             SweepParams P0 = params(0, 0, 0, 0);
             prepare(P0, false);
         }
-        async_own0 = ev0;
-        async_own1 = ev1;
-        async_rows.clear();
+        tm.async_rows.clear();
         py.counts.resize((size_t)bound, 0);   // from here on K() is the bound
-        async_K0 = K0;
-        async_stream = stream();
-        async_active = true;
+        run.async_K0 = K0;
+        run.async_stream = stream();
+        run.async_active = true;
         pairs_ticket = 0;
     }
     // sample one batch of a device-normalised run (its events from the pool)
     void async_sample(size_t b, size_t e, uint32_t seed, uint64_t draw_base) {
-        // (events only for the batches kernel_timing picks: batch_sample's
+        // (events only for the batches opt.kernel_timing picks: batch_sample's
         // own rule, looked at before it counts the batch)
         const bool will_time =
-            e > b && kernel_timing > 0
-            && timing_tick % (uint64_t)kernel_timing == 0;
-        if (will_time) {
-            const size_t i = async_rows.size();
-            while (ev_pool.size() < 2 * (i + 1)) {
-                hipEvent_t ev = nullptr;
-                HIP_CHECK(hipEventCreate(&ev));
-                ev_pool.push_back(ev);
-            }
-            ev0 = ev_pool[2 * i];
-            ev1 = ev_pool[2 * i + 1];
-        }
+            e > b && opt.kernel_timing > 0
+            && tm.timing_tick % (uint64_t)opt.kernel_timing == 0;
+        if (will_time) tm.use_run_pair();
         batch_sample(b, e, seed, draw_base);
         DIST_REQUIRE(e == b || batch_value_sorted,
                      "internal: device-normalised run left its path");
-        if (will_time) async_rows.push_back(e - b);
-        run_batches += 1;
-        async_batches += 1;
+        if (will_time) tm.async_rows.push_back(e - b);
+        run.run_batches += 1;
+        run.async_batches += 1;
     }
     // back to host-driven operation; `failed`: on the way out of an error
     void async_end(bool failed) {
-        ev0 = async_own0;
-        ev1 = async_own1;
-        timing_pending = false;
+        tm.use_own_pair();
+        tm.timing_pending = false;
         if (failed) {
             batch_open = false;
             (void)hipStreamSynchronize(stream());
-            async_active = false;
+            run.async_active = false;
             tracker.repacked += 1;   // (recorded offsets: not to be trusted)
             try { pull_host_state(); } catch (...) {}
             return;
         }
         try {
-            pull_host_state();   // (reads dev_state: K() is still the bound)
+            // (reads run.dev_state: K() is still the bound)
+            pull_host_state();
         } catch (...) {
             // the mirrors are unknown: every later call on this engine fails
             poisoned = true;
-            async_active = false;
+            run.async_active = false;
             throw;
         }
-        // (a sharded run: remember what it had left, see resume_bound)
-        resume_bound = sharded_batches ? (size_t)async_bound_K : 0;
-        resume_left = sharded_batches ? async_left : 0;
-        resume_K0 = run_origin_K0;
-        resume_done = run_origin_done;
-        async_active = false;
-        collect_comm_timing();
-        for (size_t i = 0; i < async_rows.size(); ++i) {
-            if (!async_rows[i]) continue;
-            float ms = 0.f;
-            HIP_CHECK(hipEventElapsedTime(&ms, ev_pool[2 * i],
-                                          ev_pool[2 * i + 1]));
-            kernel_ms += ms;
-            kernel_launches += 1;
-            kernel_rows += async_rows[i];
-        }
+        // (a sharded run: remember what it had left, see run.resume_bound)
+        run.resume_bound = run.sharded_batches ? (size_t)run.async_bound_K : 0;
+        run.resume_left = run.sharded_batches ? run.async_left : 0;
+        run.resume_K0 = run.run_origin_K0;
+        run.resume_done = run.run_origin_done;
+        run.async_active = false;
+        tm.collect_comm_timing();
+        tm.collect_run();
     }
     void sweep_async(size_t r0, size_t r1, size_t batch, uint32_t seed,
                      uint64_t draw_base) {
         const size_t n_batches = (r1 - r0 + batch - 1) / batch;
-        if (!async_active) {   // else: it goes on
+        if (!run.async_active) {   // else: it goes on
             // (the first range sorted now rather than by its first batch:
             // what it looks like decides how long a run is opened)
             const size_t e0 = std::min(r1, r0 + batch);
             drop_overlapping_caches(r0, e0, true);
             vs_get(r0, e0);
             async_begin(n_batches, vs_expect_fused(r0, e0));
-            sharded_batches = sharded_batch_rows = 0;   // (not a sharded run)
+            // (not a sharded run)
+            run.sharded_batches = run.sharded_batch_rows = 0;
         }
-        async_left -= n_batches;
+        run.async_left -= n_batches;
         async_peek_collect();
         try {
             for (size_t b = r0; b < r1; b += batch) {
@@ -4456,11 +4520,11 @@ struct Gibbs {
     }
     // may this sweep go on with the open device-normalised run?
     bool async_continues(size_t r0, size_t r1, size_t batch) const {
-        if (device_normalise_mode == 0 || r1 <= r0) return false;
+        if (opt.device_normalise_mode == 0 || r1 <= r0) return false;
         const size_t last = (r1 - r0) % batch;
         if (!use_value_sorted(std::min(batch, r1 - r0))) return false;
         if (last && !use_value_sorted(last)) return false;
-        return (r1 - r0 + batch - 1) / batch <= async_left;
+        return (r1 - r0 + batch - 1) / batch <= run.async_left;
     }
     // the host's mirrors are current again (every entry point but sweep()
     // comes through here: dist_gibbs::impl)
@@ -4469,13 +4533,14 @@ struct Gibbs {
         DIST_REQUIRE(!poisoned, "engine state lost: an open device-normalised "
                                 "run failed to close, or the ranks diverged "
                                 "(see the earlier error)");
-        if (async_active && !batch_open) async_end(false);
+        if (run.async_active && !batch_open) async_end(false);
         check_comm_fault();
     }
     // the sharded loop (dist_gibbs_sweep_sharded): rank-local conditions; the
     // ranks must agree before they rely on it (engine.ShardedGibbs)
     bool async_eligible_sharded(size_t n_batches, size_t batch) const {
-        if (device_normalise_mode == 0 || cluster != 0 || F() != 1) return false;
+        if (opt.device_normalise_mode == 0 || cluster != 0 || F() != 1)
+            return false;
         if (!n_batches || any_float_stats() || py.n_empty < 1) return false;
         for (size_t b = 0; b < n_batches; ++b) {
             const size_t r0 = std::min(n_rows, b * batch);
@@ -4495,9 +4560,9 @@ struct Gibbs {
         // closed and not taken up again -- this rank's next sharded pass asks
         // its peers for a new one, and if they did not sweep likewise the
         // exchange's header tells, sharded_header)
-        if (async_active && sharded_batches) settle();
-        forget_resume();
-        if (async_active) {   // an open run: go on with it, or close it
+        if (run.async_active && run.sharded_batches) settle();
+        run.forget_resume();
+        if (run.async_active) {   // an open run: go on with it, or close it
             if (async_continues(r0, r1, batch)) {
                 sweep_async(r0, r1, batch, seed, draw_base);
                 return;
@@ -4570,7 +4635,7 @@ struct Gibbs {
     static constexpr int kChainRoom = 256;   // groups a launch may found
     static constexpr uint32_t kChainIds = 4096;   // ... and ids it may issue
     bool chain_fits() const {
-        return sequential_mode == 2
+        return opt.sequential_mode == 2
                && chains_lds(K() + kChainRoom) <= kLdsNoOptIn;
     }
     size_t chain_lds_bytes() const {
@@ -4603,7 +4668,7 @@ struct Gibbs {
         st.global_size = (uint32_t)tracker.g2p.size();
         st.first_new_global = st.global_size;
         st.nonempty = K() - py.n_empty;
-        dev_state.upload(&st, 1);
+        run.dev_state.upload(&st, 1);
         chain_result.reserve(1, 0);
         ChainArgs A;
         memset(&A, 0, sizeof(A));
@@ -4613,7 +4678,7 @@ struct Gibbs {
         A.assign = assign;
         A.p2g = d_maps.p;
         A.g2p = reinterpret_cast<int32_t *>(d_maps.p + maps_pcap);
-        A.dev = dev_state.p;
+        A.dev = run.dev_state.p;
         A.result = chain_result.p;
         A.rng_state = rng;
         A.k_room = room;
@@ -4640,7 +4705,7 @@ struct Gibbs {
                       "slot head too small");
         HIP_CHECK(hipMemcpyAsync(slot, chain_result.p, sizeof(ChainResult),
                                  hipMemcpyDeviceToHost, stream()));
-        HIP_CHECK(hipMemcpyAsync(slot + sizeof(ChainResult), dev_state.p,
+        HIP_CHECK(hipMemcpyAsync(slot + sizeof(ChainResult), run.dev_state.p,
                                  sizeof(DevState), hipMemcpyDeviceToHost,
                                  stream()));
         HIP_CHECK(hipMemcpyAsync(slot + kChainSlotHead, py.d_counts.p,
@@ -4684,17 +4749,9 @@ struct Gibbs {
     }
     // pinned memory for the slots of a launch's engines (per thread, grown)
     static char * chain_pinned(size_t bytes) {
-        static thread_local char * p = nullptr;
-        static thread_local size_t cap = 0;
-        if (bytes > cap) {
-            if (p) (void)hipHostFree(p);
-            p = nullptr;
-            cap = 0;
-            const size_t want = grow_capacity(bytes);
-            HIP_CHECK(hipHostMalloc((void **)&p, want, hipHostMallocDefault));
-            cap = want;
-        }
-        return p;
+        static thread_local PinnedBuf<char> buf;
+        buf.reserve(bytes, hipHostMallocDefault);
+        return buf.p;
     }
     ChainResult chain_collect() {
         const int room = K() + kChainRoom;
@@ -4737,7 +4794,7 @@ struct Gibbs {
     uint64_t chain_launches = 0;
     void sweep_sequential(size_t r0, size_t r1, uint32_t * rng_state) {
         DIST_REQUIRE(!batch_open, "previous batch not finished");
-        resume_bound = resume_left = 0;
+        run.resume_bound = run.resume_left = 0;
         DIST_REQUIRE(r0 <= r1 && r1 <= n_rows, "bad row range");
         DIST_REQUIRE(r1 <= assigned_rows || r0 == r1,
                      "rows without a group yet: init_sequential first");
@@ -4758,7 +4815,8 @@ struct Gibbs {
                 continue;
             }
             if (chain_rows_lds(K()) > kLdsStripLimit
-                || sequential_mode == 0) {   // scores do not fit one LDS strip
+                || opt.sequential_mode == 0) {
+                // (scores do not fit one LDS strip)
                 sequential_row_as_batch(r, rng_state);
                 r += 1;
                 continue;
@@ -4847,9 +4905,6 @@ struct Gibbs {
         row_scores.download(out, (size_t)n);
         *size_out = (size_t)n;
     }
-    // k_score_rows takes one work-item per (row, group): a launch covers at
-    // most this many (debug.score_rows_chunk lowers it), whole rows each
-    int score_rows_chunk = 1 << 30;
     void score_rows(size_t r0, size_t r1, float * out_dev, size_t ld) {
         DIST_REQUIRE(r0 <= r1 && r1 <= n_rows && ld >= (size_t)K(),
                      "bad row range or leading dimension");
@@ -4862,7 +4917,7 @@ struct Gibbs {
         SweepParams P = params(r0, r1, 0, 0);
         prepare(P);
         const size_t step =
-            std::max<size_t>(1, (size_t)score_rows_chunk / (size_t)K());
+            std::max<size_t>(1, (size_t)opt.score_rows_chunk / (size_t)K());
         for (size_t c0 = r0; c0 < r1; c0 += step) {
             const size_t c1 = std::min(r1, c0 + step);
             P.row_begin = c0;
@@ -4872,9 +4927,7 @@ struct Gibbs {
         }
     }
 
-    // Held-out rows (kernels_predict.h): one lane per query row, launched in
-    // chunks of at most this many whole rows (debug.predict_chunk lowers it)
-    int predict_chunk = 1 << 22;
+    // Held-out rows (kernels_predict.h): one lane per query row
     DeviceBuf<float> predict_prior;
     DeviceBuf<SampleOut> predict_total;
     DeviceBuf<unsigned long long> predict_bad;
@@ -4896,13 +4949,13 @@ struct Gibbs {
                      "predict: mode is 0 (draw) or 1 (first maximum)");
         // the caches it reads are the frozen state's only between batches
         DIST_REQUIRE(!batch_open, "batch open");
-        require_whole("predict");
+        ex.require_whole("predict");
         if (n == 0) return;
         DIST_REQUIRE(values_dev != nullptr || F() == 0, "null argument");
         for (int f = 0; f < F(); ++f)
             DIST_REQUIRE(values_dev[f] != nullptr, "null value column");
         upload_maps();
-        const size_t step = std::min(n, (size_t)predict_chunk);
+        const size_t step = std::min(n, (size_t)opt.predict_chunk);
         ensure_pow_tables(step);
         SweepParams P = params(0, 0, seed_state, draw_base);
         prepare_base(P);
@@ -4963,11 +5016,11 @@ struct Gibbs {
         Gibbs * open = this;
         open->check_comm_fault();
         auto agree = [&](Gibbs & e, int mine) {
-            e.agree_flag.reserve(1, 0);
-            HIP_CHECK(hipMemcpyAsync(e.agree_flag.p, &mine, sizeof(int),
+            e.ex.agree_flag.reserve(1, 0);
+            HIP_CHECK(hipMemcpyAsync(e.ex.agree_flag.p, &mine, sizeof(int),
                                      hipMemcpyHostToDevice, stream()));
-            c->all_reduce(e.agree_flag.p, 1, COMM_I32, COMM_MIN, stream());
-            e.agree_flag.download(&mine, 1);
+            c->all_reduce(e.ex.agree_flag.p, 1, COMM_I32, COMM_MIN, stream());
+            e.ex.agree_flag.download(&mine, 1);
             return mine != 0;
         };
         // Does the ranks' run go on?  Decided by every rank for itself, from
@@ -4976,7 +5029,7 @@ struct Gibbs {
         // open goes on with it; a rank that closed it between the passes by
         // LOOKING at its state (the entry points that read: GibbsRef::read)
         // takes it up again with the same bound, the same batches left and
-        // the same origin (resume_bound): its collectives are the ones its
+        // the same origin (run.resume_bound): its collectives are the ones its
         // peers issue.  No word between the ranks, no host round trip at the
         // start of a pass (round 4 agreed on every call: 50 us per pass,
         // profiles/r5_collective_pass.txt).  Only when the run is used up, on
@@ -4986,63 +5039,66 @@ struct Gibbs {
         // for a new one here while its peers go on: a caller's error, told by
         // the host transport at once (collectives of different sizes) and,
         // where the sizes happen to agree, by the exchange's header.
-        const bool tiling_same = open->sharded_batches == n_batches
-                                 && open->sharded_batch_rows == batch_rows;
+        const bool tiling_same = open->run.sharded_batches == n_batches
+                                 && open->run.sharded_batch_rows == batch_rows;
         bool on_device = false;
-        if (open->async_active && !open->batch_open && tiling_same
-            && n_batches <= open->async_left) {
+        if (open->run.async_active && !open->batch_open && tiling_same
+            && n_batches <= open->run.async_left) {
             on_device = true;
-        } else if (!open->async_active && !open->batch_open && tiling_same
-                   && open->resume_bound && n_batches <= open->resume_left
-                   && (size_t)open->K() + open->resume_left
-                              * (size_t)open->py.n_empty <= open->resume_bound
-                   && open->sharded_device_normalise
+        } else if (!open->run.async_active && !open->batch_open && tiling_same
+                   && open->run.resume_bound
+                   && n_batches <= open->run.resume_left
+                   && (size_t)open->K()
+                              + open->run.resume_left
+                                    * (size_t)open->py.n_empty
+                          <= open->run.resume_bound
+                   && open->opt.sharded_device_normalise
                    && open->async_eligible_sharded(n_batches, batch_rows)) {
-            const size_t bound = open->resume_bound, left = open->resume_left;
+            const size_t bound = open->run.resume_bound,
+                         left = open->run.resume_left;
             open->async_begin(n_batches, true, bound, left);
-            open->resumed_runs += 1;
+            open->run.resumed_runs += 1;
             on_device = true;
         }
         if (!on_device) {
             settle();   // (closes an open run and forgets it: GibbsRef's ->)
-            forget_resume();
+            run.forget_resume();
             Gibbs & s = *this;
             on_device = agree(
-                s, s.sharded_device_normalise
+                s, s.opt.sharded_device_normalise
                        && s.async_eligible_sharded(n_batches, batch_rows)
                    ? 1 : 0);
-            s.sharded_run_serial += 1;
+            s.run.sharded_run_serial += 1;
             if (on_device) {
                 // (the run's bound on the group count sizes the buffers: the
                 // same on every rank, so not a function of what this rank's
                 // ranges look like)
                 s.async_begin(n_batches);
-                s.sharded_batches = n_batches;
-                s.sharded_batch_rows = batch_rows;
+                s.run.sharded_batches = n_batches;
+                s.run.sharded_batch_rows = batch_rows;
             } else {
-                s.sharded_batches = s.sharded_batch_rows = 0;
+                s.run.sharded_batches = s.run.sharded_batch_rows = 0;
             }
         }
         Gibbs & e = *open;
         if (on_device) {
-            e.async_left -= std::min(e.async_left, n_batches);
+            e.run.async_left -= std::min(e.run.async_left, n_batches);
             e.async_peek_collect();
         }
-        if (!e.comm_fault) {
-            HIP_CHECK(hipHostMalloc((void **)&e.comm_fault, sizeof(unsigned),
-                                    hipHostMallocDefault));
-            *e.comm_fault = 0;
+        if (!e.ex.comm_fault.p) {
+            e.ex.comm_fault.alloc(1, hipHostMallocDefault);
+            *e.ex.comm_fault.p = 0;
         }
         const int ne = e.py.n_empty;
         // where this rank believes the ranks' run stands at batch `done` of
         // it, exchanging `kx` groups: two 12-bit signatures
         auto signature = [&](size_t done, size_t kx, uint64_t & tag) {
-            uint64_t h = mix64(e.sharded_run_serial);
+            uint64_t h = mix64(e.run.sharded_run_serial);
             h = mix64(h ^ (uint64_t)done);
             h = mix64(h ^ (uint64_t)kx);
             h = mix64(h ^ (uint64_t)n_batches);
             h = mix64(h ^ (uint64_t)batch_rows);
-            h = mix64(h ^ (uint64_t)(e.value_partitioned ? 1 : 0));
+            h = mix64(h ^ (uint64_t)(e.ex.value_partitioned ? 1 : 0));
             h = mix64(h ^ (uint64_t)(on_device ? 1 : 0));
             tag = h | 1ull;
             return std::make_pair((int32_t)(h & 0xFFF),
@@ -5055,63 +5111,68 @@ struct Gibbs {
                 // the groups this batch's deltas can touch: rank-independent
                 // (the run's bound only sizes buffers, see exchange_K)
                 const size_t kx = e.exchange_K();
-                const size_t done = on_device ? e.run_origin_done : b;
+                const size_t done = on_device ? e.run.run_origin_done : b;
                 if (on_device) e.async_sample(r0, r1, seed_state, draw_base);
                 else e.batch_sample(r0, r1, seed_state, draw_base);
                 const size_t words = e.exchange_words(kx);
                 const size_t total = kCommHeaderWords + words;
                 // the exchange buffer is zeroed once; k_add_words clears what
                 // it consumes, so it is all zero again before every batch
-                if (total > e.delta_image.cap || !e.delta_image.p) {
-                    e.delta_image.reserve(grow_capacity(total), 0);
-                    HIP_CHECK(hipMemsetAsync(e.delta_image.p, 0,
-                                             e.delta_image.cap * 4, stream()));
-                    e.delta_header_tag = 0;
+                if (total > e.ex.delta_image.cap || !e.ex.delta_image.p) {
+                    e.ex.delta_image.reserve(grow_capacity(total), 0);
+                    HIP_CHECK(hipMemsetAsync(e.ex.delta_image.p, 0,
+                                             e.ex.delta_image.cap * 4,
+                                             stream()));
+                    e.ex.delta_header_tag = 0;
                 }
-                int32_t * image = e.delta_image.p + kCommHeaderWords;
+                int32_t * image = e.ex.delta_image.p + kCommHeaderWords;
                 uint64_t tag = 0;
                 const auto sig = signature(done, kx, tag);
-                if (e.delta_header_tag != tag)   // (not left by the last batch)
+                // (not left by the last batch)
+                if (e.ex.delta_header_tag != tag)
                     hipLaunchKernelGGL(k_comm_header, dim3(1), dim3(1), 0,
-                                       stream(), e.delta_image.p, sig.first,
+                                       stream(), e.ex.delta_image.p, sig.first,
                                        sig.second);
                 e.batch_delta_exchange(image, kx);
                 // in place, on the engine's stream: no hop to another stream
-                const bool timed = e.kernel_timing > 0
-                                   && e.comm_tick++ % (uint64_t)e.kernel_timing
-                                          == 0;
-                hipEvent_t t0 = nullptr, t1 = nullptr;
+                const bool timed =
+                    e.opt.kernel_timing > 0
+                    && e.tm.comm_tick++ % (uint64_t)e.opt.kernel_timing == 0;
+                Event t0, t1;
                 if (timed) {
-                    t0 = e.comm_event();
-                    t1 = e.comm_event();
-                    HIP_CHECK(hipEventRecord(t0, stream()));
+                    t0 = e.tm.comm_event();
+                    t1 = e.tm.comm_event();
+                    HIP_CHECK(hipEventRecord(t0.e, stream()));
                 }
-                c->all_reduce(e.delta_image.p, total, COMM_I32, COMM_SUM,
+                c->all_reduce(e.ex.delta_image.p, total, COMM_I32, COMM_SUM,
                               stream());
-                e.comm_collectives += 1;
-                e.comm_words_total += total;
-                e.comm_words_last = total;
-                e.comm_words_max = std::max<uint64_t>(e.comm_words_max, total);
+                e.ex.comm_collectives += 1;
+                e.ex.comm_words_total += total;
+                e.ex.comm_words_last = total;
+                e.ex.comm_words_max =
+                    std::max<uint64_t>(e.ex.comm_words_max, total);
                 if (timed) {
-                    HIP_CHECK(hipEventRecord(t1, stream()));
-                    e.comm_ev_pending.emplace_back(t0, t1);
+                    HIP_CHECK(hipEventRecord(t1.e, stream()));
+                    e.tm.comm_ev_pending.emplace_back(std::move(t0),
+                                                   std::move(t1));
                 }
                 // the kernel that consumes the sum checks the header and
                 // leaves the NEXT batch's behind (no launch of its own then)
                 CommCheck chk;
                 memset(&chk, 0, sizeof(chk));
-                chk.header = e.delta_image.p;
+                chk.header = e.ex.delta_image.p;
                 chk.world = c->world;
-                chk.fault = e.comm_fault;
-                chk.tag = (unsigned)(e.comm_collectives & 0x7FFFFFFFu)
+                chk.fault = e.ex.comm_fault.p;
+                chk.tag = (unsigned)(e.ex.comm_collectives & 0x7FFFFFFFu)
                           | 0x80000000u;
-                e.delta_header_tag = 0;
+                e.ex.delta_header_tag = 0;
                 if (b + 1 < n_batches) {
                     const size_t kx_next =
                         on_device ? std::min<size_t>(
                                         (size_t)e.K(),
-                                        e.run_origin_K0
-                                            + (e.run_origin_done + 1) * (size_t)ne)
+                                        e.run.run_origin_K0
+                                            + (e.run.run_origin_done + 1)
+                                                  * (size_t)ne)
                                   : 0;
                     if (on_device) {
                         uint64_t tag_next = 0;
@@ -5120,11 +5181,12 @@ struct Gibbs {
                         chk.next[1] = nx.first * nx.first;
                         chk.next[2] = nx.second;
                         chk.next[3] = nx.second * nx.second;
-                        e.delta_header_tag = tag_next;
+                        e.ex.delta_header_tag = tag_next;
                     }
                 }
-                e.batch_apply_words(image, true, kx, !e.value_partitioned, chk);
-                if (on_device) e.run_origin_done += 1;
+                e.batch_apply_words(image, true, kx,
+                                    !e.ex.value_partitioned, chk);
+                if (on_device) e.run.run_origin_done += 1;
                 if (e.merged_floats()) {   // the float statistics as sums
                     e.merge_float_delta();
                     c->all_reduce(e.merge_image.p,
@@ -5142,7 +5204,7 @@ struct Gibbs {
         }
         if (!on_device) {
             dist::sync();
-            e.collect_comm_timing();
+            e.tm.collect_comm_timing();
             e.check_comm_fault();
         }
         // (an on-device run stays open: Gibbs::settle)
@@ -5169,9 +5231,9 @@ struct Gibbs {
         std::vector<int32_t> h((size_t)dim * 2);
         has.download(h.data(), h.size());
         std::vector<int32_t> owned((size_t)dim);
-        e.present_values = 0;
+        e.ex.present_values = 0;
         for (int x = 0; x < dim; ++x) {
-            e.present_values += h[x] ? 1 : 0;
+            e.ex.present_values += h[x] ? 1 : 0;
             DIST_REQUIRE(h[(size_t)dim + x] <= 1,
                          "value " + std::to_string(x) + " has rows on "
                          + std::to_string(h[(size_t)dim + x])
@@ -5179,26 +5241,26 @@ struct Gibbs {
             // (a value nobody has rows of: its cells never change; rank 0's)
             owned[x] = h[x] || (h[(size_t)dim + x] == 0 && c->rank == 0);
         }
-        e.owned_values.upload(owned.data(), owned.size());
-        e.value_partitioned = true;
+        e.ex.owned_values.upload(owned.data(), owned.size());
+        e.ex.value_partitioned = true;
         dist::sync();
     }
     void gather_cells(dist_comm_t * c) {
         Gibbs & e = *this;
-        DIST_REQUIRE(e.value_partitioned, "not a value-partitioned engine");
+        DIST_REQUIRE(e.ex.value_partitioned, "not a value-partitioned engine");
         DIST_REQUIRE(!e.batch_open, "a batch is open");
         const int dim = e.feats[0]->dim();
         const size_t cells = (size_t)e.K() * dim;
         DeviceBuf<int32_t> image;
         image.reserve(std::max<size_t>(cells, 1), 0);
         if (cells)
-            LAUNCH(k_owned_cells, cells, e.feats[0]->cnt.p, e.owned_values.p,
+            LAUNCH(k_owned_cells, cells, e.feats[0]->cnt.p, e.ex.owned_values.p,
                    cells, dim, image.p);
         c->all_reduce(image.p, cells, COMM_I32, COMM_SUM, stream());
         if (cells)
             HIP_CHECK(hipMemcpyAsync(e.feats[0]->cnt.p, image.p, cells * 4,
                                      hipMemcpyDeviceToDevice, stream()));
-        e.cells_partial = false;
+        e.ex.cells_partial = false;
         e.rebuild_caches();
         dist::sync();
     }
@@ -5235,12 +5297,12 @@ struct GibbsRef {
     // pass for one that went on)
     Gibbs * operator->() const {
         p->settle();
-        p->forget_resume();
+        p->run.forget_resume();
         return p.get();
     }
     Gibbs & operator*() const {
         p->settle();
-        p->forget_resume();
+        p->run.forget_resume();
         return *p;
     }
     Gibbs * read() const {
@@ -6091,7 +6153,7 @@ size_t dist_gibbs_stat_words(const dist_gibbs_t * g) {
 }
 int dist_gibbs_export_stats_dev(const dist_gibbs_t * g, int32_t * stats_dev) {
     return guarded([&] {
-        g->impl.read()->require_whole("export_stats");
+        g->impl.read()->ex.require_whole("export_stats");
         g->impl.read()->copy_stats(stats_dev, true);
         dist::sync();
     });
@@ -6099,10 +6161,11 @@ int dist_gibbs_export_stats_dev(const dist_gibbs_t * g, int32_t * stats_dev) {
 int dist_gibbs_import_stats_dev(dist_gibbs_t * g, const int32_t * stats_dev) {
     return guarded([&] {
         g->impl->copy_stats(const_cast<int32_t *>(stats_dev), false);
-        g->impl->resume_bound = g->impl->resume_left = 0;
+        g->impl->run.resume_bound = g->impl->run.resume_left = 0;
         g->impl->pairs_ticket = 0;   // whatever a batch published is stale now
         g->impl->early_ticket = 0;
-        g->impl->cells_partial = false;   // (whole again: the caller's image)
+        // (whole again: the caller's image)
+        g->impl->ex.cells_partial = false;
         g->impl->refresh_host_counts();
         g->impl->rebuild_caches();
         dist::sync();
@@ -6217,13 +6280,13 @@ int dist_gibbs_gather_cells(dist_gibbs_t * g, dist_comm_t * c) {
 int dist_gibbs_comm_volume(dist_gibbs_t * g, uint64_t out[4], int reset) {
     return guarded([&] {
         Gibbs * e = g->impl.open();   // (counters only: the run stays open)
-        out[0] = e->comm_collectives;
-        out[1] = e->comm_words_total;
-        out[2] = e->comm_words_max;
-        out[3] = e->comm_words_last;
+        out[0] = e->ex.comm_collectives;
+        out[1] = e->ex.comm_words_total;
+        out[2] = e->ex.comm_words_max;
+        out[3] = e->ex.comm_words_last;
         if (reset)
-            e->comm_collectives = e->comm_words_total = e->comm_words_max =
-                e->comm_words_last = 0;
+            e->ex.comm_collectives = e->ex.comm_words_total =
+                e->ex.comm_words_max = e->ex.comm_words_last = 0;
     });
 }
 
@@ -6413,7 +6476,7 @@ int dist_gibbs_get_group(const dist_gibbs_t * g, int feature, size_t groupid,
                          uint32_t * group_out) {
     return guarded([&] {
         DIST_REQUIRE(feature >= 0 && feature < g->impl.read()->F(), "bad feature");
-        g->impl.read()->require_whole("get_group");
+        g->impl.read()->ex.require_whole("get_group");
         dist::sync();
         g->impl.read()->feats[feature]->get_group(groupid, group_out);
     });
@@ -6538,124 +6601,78 @@ int dist_gibbs_sharded_device_normalise_ok(const dist_gibbs_t * g,
         *ok_out = g->impl.read()->async_eligible_sharded(n_batches, batch_rows) ? 1 : 0;
     });
 }
-// One row per option: the public ones (include/distributions_hip.h documents
-// them) and the tests' hooks, spelled "debug.<name>": each forces a kernel
-// variant the library otherwise picks by itself, and none changes a result.
+// One row per member of Gibbs::Options, which says what each value means: the
+// public ones (include/distributions_hip.h documents them) and the tests'
+// hooks, spelled "debug.<name>".
 struct GibbsOption {
     const char * name;
     bool hook;
     int lo, hi;           // accepted: lo <= value <= hi and, if set, ok(value)
     bool (*ok)(int);
     const char * accepts; // ... in words, for the error
-    int Gibbs::* member;
+    int Gibbs::Options::* member;
     bool drops_ranges;    // cached ranges were built by the old value
 };
 static const GibbsOption kGibbsOptions[] = {
     {"value_sorted", false, 0, 2, nullptr, "0, 1 or 2",
-     &Gibbs::value_sorted_mode, false},
-    // the table-free value-sorted kernel: 0 never, 1 auto, 2 always
-    // (cached ranges chose their apply chunks by it)
+     &Gibbs::Options::value_sorted_mode, false},
     {"value_stream", false, 0, 2, nullptr, "0, 1 or 2",
-     &Gibbs::value_stream_mode, true},
-    // k_vs_narrow for launches that cannot fill the chip: 0 never, 1 auto,
-    // 2 whenever the vectors fit its LDS (cached ranges carry their tile
-    // lists)
-    {"narrow_tiles", false, 0, 2, nullptr, "0, 1 or 2", &Gibbs::narrow_mode,
-     true},
-    // sweeps whose batches all take the value-sorted path normalise the
-    // group set on the device (no host round trip per batch): 0 never, 1
-    // where it applies (2, the default, is accepted as 1)
+     &Gibbs::Options::value_stream_mode, true},
+    {"narrow_tiles", false, 0, 2, nullptr, "0, 1 or 2",
+     &Gibbs::Options::narrow_mode, true},
     {"device_normalise", false, 0, 2, nullptr, "0, 1 or 2",
-     &Gibbs::device_normalise_mode, false},
-    // dist_gibbs_sweep_sharded may normalise on the device: set on EVERY
-    // rank or on none (engine.ShardedGibbs agrees on it)
+     &Gibbs::Options::device_normalise_mode, false},
     {"sharded_device_normalise", false, 0, 1, nullptr, "0 or 1",
-     &Gibbs::sharded_device_normalise, false},
-    // device-normalised runs of the value-sorted path: 1 (default) group
-    // set, caches and per-value tables in ONE launch between two batches
-    // (k_vs_tables), the handed-over rows inside k_vs_apply; 0 the separate
-    // launches
+     &Gibbs::Options::sharded_device_normalise, false},
     {"fused_tables", false, 0, 1, nullptr, "0 or 1",
-     &Gibbs::fused_tables_mode, false},
-    // HIP events around the score+sample kernel of every n-th batch feed
-    // dist_gibbs_kernel_stats: 1 (default) all, 0 none
+     &Gibbs::Options::fused_tables_mode, false},
     {"kernel_timing", false, 0, INT_MAX, nullptr, ">= 0",
-     &Gibbs::kernel_timing, false},
-    {"phase_timing", false, 0, 1, nullptr, "0 or 1", &Gibbs::phase_timing,
-     false},
+     &Gibbs::Options::kernel_timing, false},
+    {"phase_timing", false, 0, 1, nullptr, "0 or 1",
+     &Gibbs::Options::phase_timing, false},
     {"float_stats", false, 0, 1, nullptr, "0 ordered, 1 merged",
-     &Gibbs::float_stats_mode, false},
+     &Gibbs::Options::float_stats_mode, false},
     {"sampling", false, 0, 1, nullptr, "0 exact, 1 scan",
-     &Gibbs::sampling_mode, false},
+     &Gibbs::Options::sampling_mode, false},
     // ---- hooks ----
-    // 2 (default): k_chains, structural steps on the device; 1: the chain
-    // kernel that returns to the host at every structural step; 0: every
-    // row as a batch of one
     {"sequential_chain", true, 0, 2, nullptr, "0, 1 or 2",
-     &Gibbs::sequential_mode, false},
-    // launches of at least this many value tiles start each tile's total
-    // from the per-value running sums (a tuning knob: results do not depend
-    // on it)
+     &Gibbs::Options::sequential_mode, false},
     {"running_sums_min_tiles", true, 0, INT_MAX, nullptr, ">= 0",
-     &Gibbs::running_sums_min_tiles, false},
-    // k_vs_narrow's instance: 0 by launch size, 4 or 8 float4s
+     &Gibbs::Options::running_sums_min_tiles, false},
     {"narrow_read_ahead", true, 0, 8,
      [](int v) { return v == 0 || v == 4 || v == 8; }, "0, 4 or 8",
-     &Gibbs::narrow_read_ahead, false},
-    // k_vs_stream keeps the first pass's likelihoods for the second in a
-    // scratch row per tile (1, default) or computes them again
+     &Gibbs::Options::narrow_read_ahead, false},
     {"stream_scratch", true, 0, 1, nullptr, "0 or 1",
-     &Gibbs::stream_scratch_mode, false},
-    // general rows: 3 k_rows_scratch (default), 0 k_sweep_program (what
-    // feature lists beyond k_rows_scratch's table take anyway)
+     &Gibbs::Options::stream_scratch_mode, false},
     {"rows_scratch", true, 0, 3, [](int v) { return v == 0 || v == 3; },
-     "0 or 3", &Gibbs::rows_scratch_mode, false},
+     "0 or 3", &Gibbs::Options::rows_scratch_mode, false},
     {"rows_scratch_lds_log", true, 0, 1, nullptr, "0 or 1",
-     &Gibbs::rows_scratch_lds_log, false},
+     &Gibbs::Options::rows_scratch_lds_log, false},
     {"rows_scratch_block", true, 64, kScratchMaxBlock,
      [](int v) { return v % 64 == 0; }, "a multiple of 64 up to 1024",
-     &Gibbs::rows_scratch_block, false},
-    // general rows: the leading discrete features' scores from a
-    // per-(joint value, group) table, rows sorted by joint value (2:
-    // whenever the joint domain is no larger than the batch)
-    {"rows_fold", true, 0, 2, nullptr, "0, 1 or 2", &Gibbs::rows_fold_mode,
-     false},
-    // general rows' integer statistics: 1 (default) the whole image in LDS
-    // and a staging matrix where it fits, 0 global atomics on the
-    // categorical cells
-    {"apply_stage", true, 0, 1, nullptr, "0 or 1", &Gibbs::apply_stage_mode,
-     false},
-    // 1 (default): every batch outside the value-sorted path is scored by
-    // the program kernels when its tables exist
-    {"program_all", true, 0, 1, nullptr, "0 or 1", &Gibbs::program_all,
-     false},
-    // wave priorities by phase: 0 none, else 0x10000 | four levels
+     &Gibbs::Options::rows_scratch_block, false},
+    {"rows_fold", true, 0, 2, nullptr, "0, 1 or 2",
+     &Gibbs::Options::rows_fold_mode, false},
+    {"apply_stage", true, 0, 1, nullptr, "0 or 1",
+     &Gibbs::Options::apply_stage_mode, false},
+    {"program_all", true, 0, 1, nullptr, "0 or 1",
+     &Gibbs::Options::program_all, false},
     {"sample_prio", true, 0, 0x1ffff,
      [](int v) { return v == 0 || (v >> 16) == 1; }, "0 or 0x1abcd",
-     &Gibbs::sample_prio_mode, false},
+     &Gibbs::Options::sample_prio_mode, false},
     {"rows_prio", true, 0, 0x1ffff,
      [](int v) { return v == 0 || (v >> 16) == 1; }, "0 or 0x1abcd",
-     &Gibbs::rows_prio_mode, false},
-    // k_vs_apply samples a chunk's few handed-over rows while its other
-    // waves add up the moves (1, default) or before (0)
+     &Gibbs::Options::rows_prio_mode, false},
     {"apply_overlap", true, 0, 1, nullptr, "0 or 1",
-     &Gibbs::apply_overlap_mode, false},
-    // a device-normalised run covers at most this many batches (a whole
-    // number of passes, at least one); 0: as many as fit
+     &Gibbs::Options::apply_overlap_mode, false},
     {"run_batches_cap", true, 0, INT_MAX, nullptr, ">= 0",
-     &Gibbs::run_batches_cap, false},
-    // k_vs_tables folds every (value, group) cell's sampling total and the
-    // tiles skip their total pass: 0 never, 1 where the library chooses
-    // (default), 2 whenever k_vs_tables runs
+     &Gibbs::Options::run_batches_cap, false},
     {"shared_totals", true, 0, 2, nullptr, "0, 1 or 2",
-     &Gibbs::shared_totals_mode, false},
-    // the most (row, group) work-items one k_score_rows launch takes
-    // (default 2^30, under the 2^32 of a 1-D grid)
+     &Gibbs::Options::shared_totals_mode, false},
     {"score_rows_chunk", true, 1, INT_MAX, nullptr, "> 0",
-     &Gibbs::score_rows_chunk, false},
-    // the most query rows one k_predict launch takes (default 2^22)
+     &Gibbs::Options::score_rows_chunk, false},
     {"predict_chunk", true, 1, INT_MAX, nullptr, "> 0",
-     &Gibbs::predict_chunk, false},
+     &Gibbs::Options::predict_chunk, false},
 };
 int dist_gibbs_set_option(dist_gibbs_t * g, const char * name, int value) {
     return guarded([&] {
@@ -6674,7 +6691,7 @@ int dist_gibbs_set_option(dist_gibbs_t * g, const char * name, int value) {
                          && (!o->ok || o->ok(value)),
                      key + ": " + o->accepts);
         Gibbs & e = *g->impl;   // (settles an open run)
-        e.*(o->member) = value;
+        e.opt.*(o->member) = value;
         if (o->drops_ranges) e.drop_overlapping_caches(0, e.n_rows, false);
     });
 }
@@ -6690,9 +6707,9 @@ int dist_gibbs_debug_counts(dist_gibbs_t * g, uint64_t * out, size_t n) {
         Gibbs & e = *g->impl.read();
         uint64_t v[16] = {e.vs_batches, e.generic_batches, e.band_batches,
                           e.prefix_batches, 0, 0, e.stream_batches,
-                          e.async_batches, e.narrow_batches,
+                          e.run.async_batches, e.narrow_batches,
                           e.scratch_batches, e.fold_batches, e.scan_batches,
-                          e.merged_batches, e.fused_batches, e.resumed_runs,
+                          e.merged_batches, e.fused_batches, e.run.resumed_runs,
                           e.chain_launches};
         if (e.last_bands && !e.batch_open && e.vsBandMode.p) {
             // values whose arg-max group's rows had a tile of their own in
@@ -6713,12 +6730,14 @@ int dist_gibbs_phase_stats(dist_gibbs_t * g, double ms_out[5],
                            uint64_t * batches_out, int reset) {
     return guarded([&] {
         Gibbs & e = *g->impl.read();   // (settles an open run: its events are read)
-        e.collect_comm_timing();
-        for (int i = 0; i < Gibbs::kPhases; ++i) ms_out[i] = e.phase_ms[i];
-        *batches_out = e.phase_batches;
+        e.tm.collect_comm_timing();
+        for (int i = 0; i < Gibbs::Timing::kPhases; ++i)
+            ms_out[i] = e.tm.phase_ms[i];
+        *batches_out = e.tm.phase_batches;
         if (reset) {
-            for (int i = 0; i < Gibbs::kPhases; ++i) e.phase_ms[i] = 0.0;
-            e.phase_batches = 0;
+            for (int i = 0; i < Gibbs::Timing::kPhases; ++i)
+                e.tm.phase_ms[i] = 0.0;
+            e.tm.phase_batches = 0;
         }
     });
 }
@@ -6726,12 +6745,12 @@ int dist_gibbs_comm_stats(dist_gibbs_t * g, double * ms_out,
                           uint64_t * launches_out, int reset) {
     return guarded([&] {
         Gibbs & e = *g->impl.read();   // (settles an open run: its events are read)
-        e.collect_comm_timing();
-        if (ms_out) *ms_out = e.comm_ms;
-        if (launches_out) *launches_out = e.comm_launches;
+        e.tm.collect_comm_timing();
+        if (ms_out) *ms_out = e.tm.comm_ms;
+        if (launches_out) *launches_out = e.tm.comm_launches;
         if (reset) {
-            e.comm_ms = 0.0;
-            e.comm_launches = 0;
+            e.tm.comm_ms = 0.0;
+            e.tm.comm_launches = 0;
         }
     });
 }
@@ -6739,13 +6758,13 @@ int dist_gibbs_kernel_stats(dist_gibbs_t * g, double * ms_out,
                             uint64_t * launches_out, uint64_t * rows_out,
                             int reset) {
     return guarded([&] {
-        if (ms_out) *ms_out = g->impl.read()->kernel_ms;
-        if (launches_out) *launches_out = g->impl.read()->kernel_launches;
-        if (rows_out) *rows_out = g->impl.read()->kernel_rows;
+        if (ms_out) *ms_out = g->impl.read()->tm.kernel_ms;
+        if (launches_out) *launches_out = g->impl.read()->tm.kernel_launches;
+        if (rows_out) *rows_out = g->impl.read()->tm.kernel_rows;
         if (reset) {
-            g->impl.read()->kernel_ms = 0.0;
-            g->impl.read()->kernel_launches = 0;
-            g->impl.read()->kernel_rows = 0;
+            g->impl.read()->tm.kernel_ms = 0.0;
+            g->impl.read()->tm.kernel_launches = 0;
+            g->impl.read()->tm.kernel_rows = 0;
         }
     });
 }
