@@ -232,6 +232,17 @@ cdef extern from "distributions_hip.h" nogil:
     int dist_gibbs_predict(dist_gibbs_t *, size_t, const uint32_t * const *,
                            float *, uint32_t *, int, uint32_t, uint64_t,
                            float *)
+    int dist_gibbs_predict_feature_dev(dist_gibbs_t *, size_t,
+                                       const uint32_t * const *,
+                                       const uint32_t *, int,
+                                       const uint32_t *, size_t, float *,
+                                       float *, uint32_t *, int, uint32_t,
+                                       uint64_t, unsigned)
+    int dist_gibbs_predict_feature(dist_gibbs_t *, size_t,
+                                   const uint32_t * const *,
+                                   const uint32_t *, int, const uint32_t *,
+                                   size_t, float *, float *, uint32_t *, int,
+                                   uint32_t, uint64_t, unsigned)
     size_t dist_gibbs_group_count(const dist_gibbs_t *)
     size_t dist_gibbs_row_count(const dist_gibbs_t *)
     int dist_gibbs_counts(const dist_gibbs_t *, int *)
@@ -281,6 +292,7 @@ cdef extern from "distributions_hip.h" nogil:
     int dist_gibbs_hyper_stats(dist_gibbs_t *, uint64_t *)
 
 
+PREDICT_FEATURE_RECOMPUTE = 1   # DIST_PREDICT_FEATURE_RECOMPUTE
 KIND_DD = DIST_DD
 KIND_BB = DIST_BB
 KIND_GP = DIST_GP
@@ -1377,6 +1389,131 @@ cdef class GibbsEngine:
         free(ptrs)
         check(rc)
         return logp, (None if mode is None else group), total
+
+    def feature_candidates(self, int target, candidates):
+        """The candidate words of predict_feature for `target`: the list
+        given, or for None the whole domain (DD 0..dim-1, BB 0, 1, DPD
+        0..dim-1 then OTHER).  -> uint32 array"""
+        cdef SharedParams s
+        if target < 0 or target >= len(self.shareds):
+            raise RuntimeError("predict_feature: no such target feature")
+        s = self.shareds[target]
+        if candidates is not None:
+            return value_words(s.c.kind, candidates).ravel()
+        if s.c.kind == DIST_DD:
+            return np.arange(s.c.dim, dtype=np.uint32)
+        if s.c.kind == DIST_BB:
+            return np.arange(2, dtype=np.uint32)
+        if s.c.kind == DIST_DPD:
+            return np.append(np.arange(s.c.dim, dtype=np.uint32),
+                             np.uint32(0xFFFFFFFF))
+        raise RuntimeError("predict_feature: this target needs a candidate "
+                           "list")
+
+    def predict_feature_dev(self, value_ptrs, size_t n_rows,
+                            size_t observed_ptr, int target, candidates,
+                            size_t joint_ptr, size_t base_ptr,
+                            size_t choice_ptr, int mode, uint32_t seed_state,
+                            draw_base=0, unsigned flags=0):
+        """One feature's predictive given the others
+        (dist_gibbs_predict_feature_dev): value_ptrs are device addresses of
+        one column of n_rows words per feature (0 for the target's is fine),
+        observed_ptr the device address of the rows' masks or 0, candidates a
+        host list or None (the whole domain), joint_ptr [n_rows, C] / base_ptr
+        / choice_ptr device addresses or 0."""
+        cdef int n = len(self.shareds)
+        if len(value_ptrs) != n:
+            raise RuntimeError("one value column per feature")
+        cdef cnp.ndarray[cnp.uint32_t, ndim=1] cand = np.ascontiguousarray(
+            self.feature_candidates(target, candidates), dtype=np.uint32)
+        cdef size_t n_cand = cand.shape[0]
+        cdef const uint32_t * cand_p = (
+            NULL if candidates is None else <const uint32_t *> cand.data)
+        cdef const uint32_t ** ptrs = <const uint32_t **> malloc(
+            sizeof(void *) * (n + 1))
+        cdef int i
+        cdef size_t addr
+        for i in range(n):
+            addr = value_ptrs[i]
+            ptrs[i] = <const uint32_t *> addr
+        cdef uint64_t db = <uint64_t> draw_base
+        cdef int rc
+        with nogil:
+            rc = dist_gibbs_predict_feature_dev(
+                self.ptr, n_rows, ptrs, <const uint32_t *> observed_ptr,
+                target, cand_p, n_cand, <float *> joint_ptr,
+                <float *> base_ptr, <uint32_t *> choice_ptr, mode, seed_state,
+                db, flags)
+        free(ptrs)
+        check(rc)
+
+    def predict_feature(self, values, int target, candidates, observed, mode,
+                        uint32_t seed_state, draw_base=0, unsigned flags=0):
+        """One feature's predictive given the others, from host arrays
+        (dist_gibbs_predict_feature): values is one array per feature (None
+        for the target's is fine), candidates a list or None (the whole
+        domain), observed one uint32 mask per row or None, mode 0 draws, 1
+        takes the first maximum, None leaves the choice out.
+        -> (joint [n, C], base [n], choice [n] or None)"""
+        cdef int n = len(self.shareds)
+        if len(values) != n:
+            raise RuntimeError("one value column per feature")
+        cdef cnp.ndarray[cnp.uint32_t, ndim=1] cand = np.ascontiguousarray(
+            self.feature_candidates(target, candidates), dtype=np.uint32)
+        cdef size_t n_cand = cand.shape[0]
+        cdef const uint32_t * cand_p = (
+            NULL if candidates is None else <const uint32_t *> cand.data)
+        cdef const uint32_t ** ptrs = <const uint32_t **> malloc(
+            sizeof(void *) * (n + 1))
+        cdef cnp.ndarray[cnp.uint32_t, ndim=1] w
+        cdef SharedParams s
+        words = []
+        cdef int i
+        cdef Py_ssize_t rows = -1
+        for i in range(n):
+            if values[i] is None and i == target:
+                ptrs[i] = NULL
+                continue
+            s = self.shareds[i]
+            w = value_words(s.c.kind, values[i])
+            if rows >= 0 and w.shape[0] != rows:
+                free(ptrs)
+                raise RuntimeError("feature columns differ in length")
+            rows = w.shape[0]
+            words.append(w)
+            ptrs[i] = <const uint32_t *> w.data
+        cdef cnp.ndarray[cnp.uint32_t, ndim=1] mask
+        cdef const uint32_t * mask_p = NULL
+        if observed is not None:
+            mask = np.ascontiguousarray(observed, dtype=np.uint32)
+            if rows >= 0 and mask.shape[0] != rows:
+                free(ptrs)
+                raise RuntimeError("one mask per row")
+            rows = mask.shape[0]
+            mask_p = <const uint32_t *> mask.data
+        if rows < 0:
+            free(ptrs)
+            raise RuntimeError("predict_feature: no column tells the number "
+                               "of rows")
+        cdef size_t n_rows = rows
+        cdef cnp.ndarray[cnp.float32_t, ndim=2] joint = np.zeros(
+            (rows, n_cand), np.float32)
+        cdef cnp.ndarray[cnp.float32_t, ndim=1] base = np.zeros(
+            rows, np.float32)
+        cdef cnp.ndarray[cnp.uint32_t, ndim=1] choice = np.zeros(
+            rows, np.uint32)
+        cdef uint32_t * cp = NULL if mode is None else <uint32_t *> choice.data
+        cdef int m = 0 if mode is None else mode
+        cdef uint64_t db = <uint64_t> draw_base
+        cdef int rc
+        with nogil:
+            rc = dist_gibbs_predict_feature(
+                self.ptr, n_rows, ptrs, mask_p, target, cand_p, n_cand,
+                <float *> joint.data, <float *> base.data, cp, m, seed_state,
+                db, flags)
+        free(ptrs)
+        check(rc)
+        return joint, base, (None if mode is None else choice)
 
     def group_count(self):
         return checked_size(dist_gibbs_group_count(self.ptr))

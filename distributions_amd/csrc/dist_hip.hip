@@ -1268,7 +1268,8 @@ struct Gibbs {
         // at most this many, whole rows each (default 2^30, under the 2^32 of
         // a 1-D grid)
         int score_rows_chunk = 1 << 30;
-        // the most query rows one k_predict launch takes, whole rows each
+        // the most query rows one k_predict or k_predict_feature launch
+        // takes, whole rows each
         int predict_chunk = 1 << 22;
     };
     Options opt;
@@ -4999,6 +5000,167 @@ struct Gibbs {
                          + std::to_string(bad & 0xFF));
     }
 
+    // One feature's predictive given the others (kernels_feature.h)
+    DeviceBuf<uint32_t> feature_cand;
+    DeviceBuf<float> feature_joint;   // [chunk][C]: choice without joint
+    // the most floats of feature_joint: scratch stays under 1 GiB
+    static constexpr size_t kFeatureScratchFloats = ((size_t)1 << 28) - 1;
+    // the LDS one workgroup of k_predict_feature starts from: under
+    // kLdsNoOptIn, so that two workgroups fit a CU
+    static constexpr size_t kFeatureLdsBudget = 48 * 1024;
+    template <int TK>
+    void launch_feature_staged(const SweepParams & P, FeatureArgs A,
+                               int terms_after) {
+        // (row, slot) items per workgroup, and the rows they can touch
+        const size_t S = (size_t)A.C + 1;
+        size_t items = kBlock;
+        if ((items - 1) / S + 2 > (size_t)kFeatureRowsMax)
+            items = (size_t)(kFeatureRowsMax - 2) * S + 1;
+        int rows = (int)((items - 1) / S + 2);
+        rows = (int)std::min<size_t>((size_t)rows, P.row_end + 1);
+        const size_t per_k = predict_feature_lds(terms_after, 0, rows);
+        int tile = (int)std::min<size_t>((size_t)P.K,
+                                         kFeatureLdsBudget / per_k - 1);
+        A.items = (int)items;
+        A.rows = rows;
+        A.tile = std::max(tile, 1);
+        const size_t lds = predict_feature_lds(terms_after, A.tile, rows);
+        const size_t blocks = (P.row_end * S + items - 1) / items;
+        launch_lds<&k_predict_feature<TK>>(dim3((unsigned)blocks),
+                                           dim3(kBlock), lds, P, A);
+    }
+    void predict_feature(size_t n, const uint32_t * const * values_dev,
+                         const uint32_t * observed_dev, int target,
+                         const uint32_t * candidates, size_t n_candidates,
+                         float * joint_dev, float * base_dev,
+                         uint32_t * choice_dev, int mode, uint32_t seed_state,
+                         uint64_t draw_base, unsigned flags) {
+        DIST_REQUIRE(mode == 0 || mode == 1,
+                     "predict_feature: mode is 0 (draw) or 1 (first maximum)");
+        DIST_REQUIRE((flags & ~(unsigned)DIST_PREDICT_FEATURE_RECOMPUTE) == 0,
+                     "predict_feature: unknown flag");
+        DIST_REQUIRE(target >= 0 && target < F(),
+                     "predict_feature: no such target feature");
+        // the caches it reads are the frozen state's only between batches
+        DIST_REQUIRE(!batch_open, "batch open");
+        ex.require_whole("predict_feature");
+        // the candidate words, validated before any launch
+        const dist_shared_t & tsh = feats[target]->sh;
+        std::vector<uint32_t> cand;
+        if (candidates == nullptr) {
+            DIST_REQUIRE(is_cat(tsh.kind) || tsh.kind == DIST_BB,
+                         "predict_feature: this target needs a candidate "
+                         "list");
+            const uint32_t dim = tsh.kind == DIST_BB ? 2u : (uint32_t)tsh.dim;
+            for (uint32_t v = 0; v < dim; ++v) cand.push_back(v);
+            if (tsh.kind == DIST_DPD) cand.push_back(DIST_DPD_OTHER);
+        } else {
+            DIST_REQUIRE(n_candidates > 0 && n_candidates < ((size_t)1 << 24),
+                         "predict_feature: bad candidate count");
+            cand.assign(candidates, candidates + n_candidates);
+            for (size_t c = 0; c < cand.size(); ++c) {
+                const bool bad_c =
+                    (tsh.kind == DIST_DD && cand[c] >= (uint32_t)tsh.dim)
+                    || (tsh.kind == DIST_BB && cand[c] > 1u);
+                DIST_REQUIRE(!bad_c,
+                             "predict_feature: candidate "
+                                 + std::to_string(c)
+                                 + " is outside the target's domain");
+                // dpd.hpp:534-542: a value the table does not hold is OTHER
+                if (tsh.kind == DIST_DPD && cand[c] >= (uint32_t)tsh.dim)
+                    cand[c] = DIST_DPD_OTHER;
+            }
+        }
+        if (n == 0) return;
+        DIST_REQUIRE(values_dev != nullptr, "null argument");
+        for (int f = 0; f < F(); ++f)
+            DIST_REQUIRE(values_dev[f] != nullptr || f == target,
+                         "null value column");
+        const size_t C = cand.size();
+        const bool scratch = choice_dev != nullptr && joint_dev == nullptr;
+        // candidates the kernel scores: none when only `base` is asked for
+        const int Ck = joint_dev != nullptr || choice_dev != nullptr ? (int)C
+                                                                      : 0;
+        size_t step = std::min(n, (size_t)opt.predict_chunk);
+        if (scratch)
+            step = std::min(step,
+                            std::max<size_t>(1, kFeatureScratchFloats / C));
+        // (the 1-D grid: at least one item per workgroup)
+        step = std::min(step,
+                        std::max<size_t>(1, (size_t)INT_MAX / (C + 1)));
+        ensure_pow_tables(step);
+        SweepParams P = params(0, 0, seed_state, draw_base);
+        prepare_base(P);
+        const size_t Kn = (size_t)K();
+        predict_prior.reserve(grow_capacity(Kn), 0);
+        LAUNCH(k_predict_prior, Kn, P, predict_prior.p);
+        feature_cand.upload(cand.data(), C);
+        if (scratch) feature_joint.reserve(step * C, 0);
+        predict_bad.reserve(1, 0);
+        HIP_CHECK(hipMemsetAsync(predict_bad.p, 0xFF, sizeof(unsigned long long),
+                                 stream()));
+        int terms_after = 0;
+        for (int f = target + 1; f < F(); ++f)
+            terms_after += is_cat(feats[f]->sh.kind) ? 2 : 1;
+        for (size_t c0 = 0; c0 < n; c0 += step) {
+            const size_t c1 = std::min(n, c0 + step);
+            for (int f = 0; f < F(); ++f)
+                P.values[f] = values_dev[f] ? values_dev[f] + c0 : nullptr;
+            P.row_begin = 0;
+            P.row_end = c1 - c0;
+            // row q draws with engine step draw_base + q + 1 of seed_state,
+            // whatever the chunking (the batch's own convention)
+            P.seed_batch = lcg_jump(seed_state, draw_base + c0 + 1ull);
+            float * joint = scratch ? feature_joint.p
+                            : joint_dev ? joint_dev + c0 * C : nullptr;
+            FeatureArgs A;
+            memset(&A, 0, sizeof(A));
+            A.prior = predict_prior.p;
+            A.observed = observed_dev ? observed_dev + c0 : nullptr;
+            A.cand = feature_cand.p;
+            A.target = target;
+            A.C = Ck;
+            A.joint = joint;
+            A.base = base_dev ? base_dev + c0 : nullptr;
+            A.q0 = (unsigned long long)c0;
+            A.bad = predict_bad.p;
+            if (flags & DIST_PREDICT_FEATURE_RECOMPUTE) {
+                LAUNCH(k_predict_feature_recompute,
+                       std::min((c1 - c0) * ((size_t)Ck + 1),
+                                (size_t)1 << 30),
+                       P, A);
+            } else {
+                switch (tsh.kind) {
+                case DIST_DD:
+                case DIST_DPD:
+                    launch_feature_staged<DIST_DD>(P, A, terms_after);
+                    break;
+                case DIST_BB:
+                    launch_feature_staged<DIST_BB>(P, A, terms_after);
+                    break;
+                case DIST_GP:
+                    launch_feature_staged<DIST_GP>(P, A, terms_after);
+                    break;
+                case DIST_BNB:
+                    launch_feature_staged<DIST_BNB>(P, A, terms_after);
+                    break;
+                default:
+                    launch_feature_staged<DIST_NICH>(P, A, terms_after);
+                    break;
+                }
+            }
+            if (choice_dev != nullptr)
+                LAUNCH(k_predict_feature_choice, c1 - c0, P, joint, (int)C,
+                       mode, choice_dev + c0);
+        }
+        unsigned long long bad = 0;
+        predict_bad.download(&bad, 1);   // (waits for the work)
+        DIST_REQUIRE(bad == ~0ull,
+                     "predict_feature: value outside its feature's domain at "
+                     "row " + std::to_string(bad >> 8) + ", feature "
+                         + std::to_string(bad & 0xFF));
+    }
+
     // ---- the ranks' loop (dist_gibbs_sweep_sharded; the caller comes in by
     // GibbsRef::open(): a run the last pass left open may go on) ------------
     void sweep_sharded(dist_comm_t * c, size_t n_batches, size_t batch_rows,
@@ -6443,6 +6605,65 @@ int dist_gibbs_predict(dist_gibbs_t * g, size_t n_rows,
                    draw_base, prior_total_out);
         if (logp_out) logp.download(logp_out, n_rows);
         if (group_out) group.download(group_out, n_rows);
+    });
+}
+int dist_gibbs_predict_feature_dev(dist_gibbs_t * g, size_t n_rows,
+                                   const uint32_t * const * values_dev,
+                                   const uint32_t * observed_dev, int target,
+                                   const uint32_t * candidates,
+                                   size_t n_candidates, float * joint_dev,
+                                   float * base_dev, uint32_t * choice_dev,
+                                   int mode, uint32_t seed_state,
+                                   uint64_t draw_base, unsigned flags) {
+    return guarded([&] {
+        g->impl.read()->predict_feature(n_rows, values_dev, observed_dev,
+                                        target, candidates, n_candidates,
+                                        joint_dev, base_dev, choice_dev, mode,
+                                        seed_state, draw_base, flags);
+    });
+}
+int dist_gibbs_predict_feature(dist_gibbs_t * g, size_t n_rows,
+                               const uint32_t * const * values,
+                               const uint32_t * observed, int target,
+                               const uint32_t * candidates,
+                               size_t n_candidates, float * joint_out,
+                               float * base_out, uint32_t * choice_out,
+                               int mode, uint32_t seed_state,
+                               uint64_t draw_base, unsigned flags) {
+    return guarded([&] {
+        Gibbs * e = g->impl.read();
+        const int F = e->F();
+        DIST_REQUIRE(target >= 0 && target < F,
+                     "predict_feature: no such target feature");
+        DIST_REQUIRE(values != nullptr || n_rows == 0, "null argument");
+        // the candidate count as the engine will see it
+        size_t C = n_candidates;
+        if (candidates == nullptr) {
+            const dist_shared_t & sh = e->feats[target]->sh;
+            C = sh.kind == DIST_BB ? 2
+                : sh.kind == DIST_DPD ? (size_t)sh.dim + 1 : (size_t)sh.dim;
+        }
+        std::vector<DeviceBuf<uint32_t>> cols((size_t)F);
+        std::vector<const uint32_t *> ptrs((size_t)F);
+        for (int f = 0; f < F && n_rows; ++f) {
+            DIST_REQUIRE(values[f] != nullptr || f == target,
+                         "null value column");
+            if (values[f] == nullptr) continue;
+            cols[f].upload(values[f], n_rows);
+            ptrs[f] = cols[f].p;
+        }
+        DeviceBuf<uint32_t> mask, choice;
+        DeviceBuf<float> joint, base;
+        if (observed && n_rows) mask.upload(observed, n_rows);
+        if (joint_out) joint.reserve(std::max<size_t>(n_rows * C, 1), 0);
+        if (base_out) base.reserve(std::max<size_t>(n_rows, 1), 0);
+        if (choice_out) choice.reserve(std::max<size_t>(n_rows, 1), 0);
+        e->predict_feature(n_rows, ptrs.data(), observed ? mask.p : nullptr,
+                           target, candidates, n_candidates, joint.p, base.p,
+                           choice.p, mode, seed_state, draw_base, flags);
+        if (joint_out) joint.download(joint_out, n_rows * C);
+        if (base_out) base.download(base_out, n_rows);
+        if (choice_out) choice.download(choice_out, n_rows);
     });
 }
 size_t dist_gibbs_group_count(const dist_gibbs_t * g) {

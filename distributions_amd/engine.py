@@ -174,6 +174,70 @@ class Gibbs(object):
             0 if m is None else m, _core.rng_seed(seed), draw_base)
         return logp, groups, total
 
+    def predict_feature(self, values, target, candidates=None, observed=None,
+                        mode="map", seed=0, draw_base=0, staged=True):
+        """Given some cells of rows that are NOT in the table, the cell that
+        is missing: feature `target`'s predictive given the others.
+        values: one host array per feature (the target's may be None; words
+        in unobserved cells are never read).  candidates: values of the
+        target to score; None takes the whole domain of a DirichletDiscrete
+        (0 .. dim-1), BetaBernoulli (0, 1) or DirichletProcessDiscrete
+        (0 .. dim-1, then OTHER) target, the other kinds need a list.
+        observed: one uint32 mask per row, bit f set when feature f of the
+        row is observed (bit `target` is ignored); None: every other feature
+        is observed.  -> (joint [n, C] float32, base [n] float32, choice [n]
+        uint32 or None):
+        joint[q, c] = log_sum_exp over all groups of the clustering model's
+        score_value, the observed features' and the target's at
+        candidates[c] (mixture.hpp:416-425, random.cc:78-92) -- the logp
+        `predict` returns for the row completed with that candidate, when
+        everything else is observed; base[q] the same with the target left
+        out, the log marginal of the observed cells.  joint - base[:, None]
+        is the log conditional of the target, under LowEntropy too.
+        choice[q] indexes the candidates: mode "sample" draws it from joint[q]
+        with engine step draw_base + q + 1 of `seed`, "map" takes the first
+        maximum, None leaves it out.  staged=False scores every (row,
+        candidate) pair from scratch (the same bits, slower where other
+        features are observed).  Nothing in the engine changes."""
+        return self.core.predict_feature(
+            list(values), target, candidates, observed,
+            self._PREDICT_MODES[mode], _core.rng_seed(seed), draw_base,
+            0 if staged else _core.PREDICT_FEATURE_RECOMPUTE)
+
+    def predict_feature_torch(self, values, target, candidates=None,
+                              observed=None, mode="map", seed=0, draw_base=0,
+                              staged=True):
+        """predict_feature for device tensors (one 4-byte-per-row CUDA tensor
+        per feature, the target's may be None; observed a CUDA int32 tensor
+        or None; candidates stay a host list): the results are tensors on the
+        same device and nothing is staged through the host.
+        -> (joint, base, choice)"""
+        import torch
+        values = [None if v is None else v.contiguous() for v in values]
+        given = [v for v in values if v is not None]
+        if observed is not None:
+            observed = observed.contiguous()
+        ref = given[0] if given else observed
+        n = int(ref.numel())
+        dev = ref.device
+        m = self._PREDICT_MODES[mode]
+        C = len(self.core.feature_candidates(target, candidates))
+        joint = torch.empty((n, C), dtype=torch.float32, device=dev)
+        base = torch.empty(n, dtype=torch.float32, device=dev)
+        choice = (torch.empty(n, dtype=torch.int32, device=dev)
+                  if m is not None else None)
+        # (the library works on its own stream: what filled the tensors on
+        # torch's must be done)
+        torch.cuda.current_stream(dev).synchronize()
+        self.core.predict_feature_dev(
+            [0 if v is None else int(v.data_ptr()) for v in values], n,
+            0 if observed is None else int(observed.data_ptr()), target,
+            candidates, int(joint.data_ptr()), int(base.data_ptr()),
+            int(choice.data_ptr()) if choice is not None else 0,
+            0 if m is None else m, _core.rng_seed(seed), draw_base,
+            0 if staged else _core.PREDICT_FEATURE_RECOMPUTE)
+        return joint, base, choice
+
     # -- hyper-parameters ---------------------------------------------------
     # The step the reference alternates with assignment sweeps
     # (mixture.hpp:427-438, then sample_from_scores and init()), on the
@@ -481,6 +545,17 @@ class ShardedGibbs(object):
         self._whole()
         return self.backend.predict(list(values), Gibbs._PREDICT_MODES[mode],
                                     seed_state, draw_base)
+
+    def predict_feature(self, values, target, candidates=None, observed=None,
+                        mode="map", seed_state=0, draw_base=0, staged=True):
+        """Each rank asks for ITS queries' missing cell against the common
+        state (as Gibbs.predict_feature; seed_state is a raw engine state).
+        A value-partitioned rank gathers its cells first."""
+        self._whole()
+        return self.backend.predict_feature(
+            list(values), target, candidates, observed,
+            Gibbs._PREDICT_MODES[mode], seed_state, draw_base,
+            0 if staged else _core.PREDICT_FEATURE_RECOMPUTE)
 
     def score_data(self):
         self._whole()

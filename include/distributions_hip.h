@@ -591,6 +591,74 @@ int dist_gibbs_predict(dist_gibbs_t * g, size_t n_rows,
                        uint32_t * group_out, int mode, uint32_t seed_state,
                        uint64_t draw_base, float * prior_total_out);
 
+/* Held-out rows: one feature's predictive given the others.  For query row q,
+ * a target feature t, candidate words cand[0..C) for t and a mask observed[q]
+ * (bit f set: feature f of row q is observed; bit t is ignored; observed ==
+ * NULL: every other feature is observed):
+ *   scores_c[k], k in [0, dist_gibbs_group_count), empty groups included: the
+ *     driver's score_value as in dist_gibbs_predict (clustering.hpp:195-208;
+ *     mixture.hpp:124-141 under LowEntropy), then in feature order
+ *     (mixture.hpp:416-425) every OBSERVED feature's score_value with the
+ *     row's value and, at position t, the target's with cand[c].  An
+ *     unobserved feature contributes nothing, not even a +0;
+ *   joint[q * C + c] = log_sum_exp(scores_c) (random.cc:78-92): the maximum,
+ *     the in-order float sum of fast_exp(s - max), fast_log(total) + max.
+ *     With every other feature observed these are the bits dist_gibbs_predict
+ *     returns as logp for the row completed with cand[c];
+ *   base[q] = log_sum_exp of the same fold with the target left out: the log
+ *     marginal of the observed cells; with nothing observed, predict's
+ *     *prior_total_out, bit for bit;
+ *   the conditional log p(x_t = cand[c] | observed cells) is joint - base,
+ *     which the caller forms; the driver's unnormalised mass under LowEntropy
+ *     cancels in it, so no prior_total is returned;
+ *   choice[q], an INDEX into the candidates: mode 0 draws it by
+ *     sample_from_scores_overwrite (random.hpp:361-366 over random.cc:94-106
+ *     and random.hpp:316-333) over joint[q][0..C) with engine step
+ *     draw_base + q + 1 of seed_state, the batch's own convention, so that
+ *     results do not depend on chunking or launch geometry; mode 1 takes the
+ *     first index of maximal joint.  joint itself is not overwritten.
+ * candidates: a HOST array of n_candidates words in both forms (counts, or
+ * float bits for NormalInverseChiSq), validated before any launch: a
+ * DirichletDiscrete word >= dim or a BetaBernoulli word > 1 fails and names
+ * the candidate's index; a DirichletProcessDiscrete word the table does not
+ * hold scores as OTHER (dpd.hpp:534-542).  candidates == NULL means the whole
+ * domain: 0 .. dim-1 (DD), 0, 1 (BB), 0 .. dim-1 then DIST_DPD_OTHER (DPD);
+ * the other kinds need a list.  C is the length of the list in use.
+ * values: F columns of n_rows words; words in unobserved cells are never
+ * interpreted and the target's column pointer may be NULL.  An OBSERVED
+ * DirichletDiscrete value >= dim or BetaBernoulli value > 1 reads nothing out
+ * of bounds: the call fails naming the first such row and its feature, and
+ * the outputs are then unspecified.  joint, base and choice may each be NULL;
+ * choice without joint keeps joint in engine scratch, the rows chunked so that
+ * it stays under 1 GiB (and under "debug.predict_chunk" rows).
+ * flags: DIST_PREDICT_FEATURE_RECOMPUTE scores every (row, candidate) pair
+ * from scratch instead of evaluating a row's candidate-independent part once
+ * (the same bits; for comparison).
+ * A pure reader under the rules of dist_gibbs_predict: nothing in the engine
+ * changes, refused while a batch is open and on a value-partitioned rank
+ * whose cells are stale; n_rows == 0 does nothing.  Returns when the work is
+ * done.
+ * _dev: values_dev is a host array of F device pointers; observed_dev, joint,
+ * base and choice are device pointers.  The host form stages, calls and
+ * downloads. */
+#define DIST_PREDICT_FEATURE_RECOMPUTE 1u
+int dist_gibbs_predict_feature_dev(dist_gibbs_t * g, size_t n_rows,
+                                   const uint32_t * const * values_dev,
+                                   const uint32_t * observed_dev, int target,
+                                   const uint32_t * candidates,
+                                   size_t n_candidates, float * joint_dev,
+                                   float * base_dev, uint32_t * choice_dev,
+                                   int mode, uint32_t seed_state,
+                                   uint64_t draw_base, unsigned flags);
+int dist_gibbs_predict_feature(dist_gibbs_t * g, size_t n_rows,
+                               const uint32_t * const * values,
+                               const uint32_t * observed, int target,
+                               const uint32_t * candidates,
+                               size_t n_candidates, float * joint_out,
+                               float * base_out, uint32_t * choice_out,
+                               int mode, uint32_t seed_state,
+                               uint64_t draw_base, unsigned flags);
+
 size_t dist_gibbs_group_count(const dist_gibbs_t * g);     /* counts().size() */
 size_t dist_gibbs_row_count(const dist_gibbs_t * g);
 int dist_gibbs_counts(const dist_gibbs_t * g, int * out);  /* driver counts() */
@@ -746,7 +814,7 @@ int dist_gibbs_sharded_device_normalise_ok(const dist_gibbs_t * g,
  *  "debug.score_rows_chunk"  n > 0: the most (row, group) work-items one
  *      dist_gibbs_score_rows_dev launch takes (2^30)
  *  "debug.predict_chunk"  n > 0: the most query rows one dist_gibbs_predict
- *      launch takes (2^22)
+ *      or dist_gibbs_predict_feature launch takes (2^22)
  */
 int dist_gibbs_set_option(dist_gibbs_t * g, const char * name, int value);
 /* how many batches each score+sample kernel has served */
