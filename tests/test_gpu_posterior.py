@@ -30,7 +30,8 @@ chain per engine and several launches per row, so they take
 f64_posterior.LEG_SAMPLES states from one engine, T sweeps apart;
 test_f64_posterior.py shows that the structural mutants are still rejected at
 p < 1e-12 at that count.  Batches of more than one row score against a
-snapshot and do not have the posterior as their stationary law: out of scope.
+snapshot and do not have the posterior as their stationary law: they are held
+to their own float64 law in test_gpu_batch_posterior.py.
 """
 import time
 
