@@ -123,6 +123,8 @@ cdef extern from "distributions_hip.h" nogil:
     int dist_group_init(const dist_shared_t *, uint32_t *)
     int dist_group_add_value(const dist_shared_t *, uint32_t *, uint32_t)
     int dist_group_remove_value(const dist_shared_t *, uint32_t *, uint32_t)
+    int dist_group_sample_value(const dist_shared_t *, const uint32_t *,
+                                uint32_t, uint64_t, size_t, int, uint32_t *)
     int dist_group_score_value(const dist_shared_t *, const uint32_t *,
                                uint32_t, float *)
     int dist_group_score_data(const dist_shared_t *, const uint32_t *, float *)
@@ -243,6 +245,14 @@ cdef extern from "distributions_hip.h" nogil:
                                    const uint32_t *, int, const uint32_t *,
                                    size_t, float *, float *, uint32_t *, int,
                                    uint32_t, uint64_t, unsigned)
+    int dist_gibbs_sample_rows_dev(dist_gibbs_t *, size_t,
+                                   const uint32_t * const *,
+                                   const uint32_t *, uint32_t * const *,
+                                   uint32_t *, uint32_t, uint64_t)
+    int dist_gibbs_sample_rows(dist_gibbs_t *, size_t,
+                               const uint32_t * const *, const uint32_t *,
+                               uint32_t * const *, uint32_t *, uint32_t,
+                               uint64_t)
     size_t dist_gibbs_group_count(const dist_gibbs_t *)
     size_t dist_gibbs_row_count(const dist_gibbs_t *)
     int dist_gibbs_counts(const dist_gibbs_t *, int *)
@@ -417,6 +427,21 @@ cdef class SharedParams:
                                      &out))
         return out
 
+    def group_sample_value(self, cnp.ndarray[cnp.uint32_t, ndim=1] g,
+                           uint32_t seed_state, row_first, size_t n,
+                           int feature):
+        """n draws from the group's posterior predictive
+        (dist_group_sample_value): the words of cells (row_first + i,
+        feature) under seed_state.  -> uint32 words"""
+        cdef cnp.ndarray[cnp.uint32_t, ndim=1] out = np.zeros(n, np.uint32)
+        cdef uint64_t r0 = <uint64_t> row_first
+        cdef int rc
+        with nogil:
+            rc = dist_group_sample_value(&self.c, <const uint32_t *> g.data,
+                                         seed_state, r0, n, feature,
+                                         <uint32_t *> out.data)
+        check(rc)
+        return out
 
     def group_score_data(self, cnp.ndarray[cnp.uint32_t, ndim=1] g):
         cdef float out = 0
@@ -1514,6 +1539,110 @@ cdef class GibbsEngine:
         free(ptrs)
         check(rc)
         return joint, base, (None if mode is None else choice)
+
+    def sample_rows_dev(self, value_ptrs, size_t n_rows, size_t observed_ptr,
+                        out_ptrs, size_t group_ptr, uint32_t seed_state,
+                        draw_base=0):
+        """Whole rows and missing cells drawn from the mixture
+        (dist_gibbs_sample_rows_dev): value_ptrs is None or one device
+        address per feature (0 for a feature no row observes), observed_ptr
+        the device address of the rows' masks or 0 (nothing observed),
+        out_ptrs one device address per feature (may equal the value's),
+        group_ptr a device address or 0."""
+        cdef int n = len(self.shareds)
+        if len(out_ptrs) != n or (value_ptrs is not None
+                                  and len(value_ptrs) != n):
+            raise RuntimeError("one column per feature")
+        cdef const uint32_t ** ptrs = <const uint32_t **> malloc(
+            sizeof(void *) * (n + 1))
+        cdef uint32_t ** outs = <uint32_t **> malloc(sizeof(void *) * (n + 1))
+        cdef int i
+        cdef size_t addr
+        for i in range(n):
+            addr = 0 if value_ptrs is None else value_ptrs[i]
+            ptrs[i] = <const uint32_t *> addr
+            addr = out_ptrs[i]
+            outs[i] = <uint32_t *> addr
+        cdef uint64_t db = <uint64_t> draw_base
+        cdef int rc
+        cdef bint no_values = value_ptrs is None
+        with nogil:
+            rc = dist_gibbs_sample_rows_dev(
+                self.ptr, n_rows, NULL if no_values else ptrs,
+                <const uint32_t *> observed_ptr, outs,
+                <uint32_t *> group_ptr, seed_state, db)
+        free(ptrs)
+        free(outs)
+        check(rc)
+
+    def sample_rows(self, n_rows, values, observed, uint32_t seed_state,
+                    draw_base=0):
+        """Whole rows and missing cells drawn from the mixture, from host
+        arrays (dist_gibbs_sample_rows): values is None or one array per
+        feature (None for a feature no row observes), observed one uint32
+        mask per row (required with values) or None: nothing observed, n_rows
+        rows.  -> (columns, groups): one completed array per feature
+        (float32 for NormalInverseChiSq, uint32 otherwise) and the drawn
+        groups as global ids"""
+        cdef int n = len(self.shareds)
+        if values is not None and len(values) != n:
+            raise RuntimeError("one value column per feature")
+        if values is not None and observed is None:
+            raise RuntimeError("sample_rows: values need an observed mask")
+        cdef cnp.ndarray[cnp.uint32_t, ndim=1] mask
+        cdef const uint32_t * mask_p = NULL
+        cdef size_t rows
+        if observed is not None:
+            mask = np.ascontiguousarray(observed, dtype=np.uint32)
+            rows = mask.shape[0]
+            mask_p = <const uint32_t *> mask.data
+        else:
+            if n_rows is None:
+                raise RuntimeError("sample_rows: neither n nor a mask tells "
+                                   "the number of rows")
+            rows = n_rows
+        if n_rows is not None and <size_t> n_rows != rows:
+            raise RuntimeError("one mask per row")
+        cdef const uint32_t ** ptrs = <const uint32_t **> malloc(
+            sizeof(void *) * (n + 1))
+        cdef uint32_t ** outs = <uint32_t **> malloc(sizeof(void *) * (n + 1))
+        cdef cnp.ndarray[cnp.uint32_t, ndim=1] w
+        cdef SharedParams s
+        words = []
+        outw = []
+        cdef int i
+        for i in range(n):
+            ptrs[i] = NULL
+            if values is not None and values[i] is not None:
+                s = self.shareds[i]
+                w = value_words(s.c.kind, values[i])
+                if <size_t> w.shape[0] != rows:
+                    free(ptrs)
+                    free(outs)
+                    raise RuntimeError("feature columns differ in length")
+                words.append(w)
+                ptrs[i] = <const uint32_t *> w.data
+            w = np.zeros(max(rows, 1), np.uint32)
+            outw.append(w)
+            outs[i] = <uint32_t *> w.data
+        cdef cnp.ndarray[cnp.uint32_t, ndim=1] group = np.zeros(
+            max(rows, 1), np.uint32)
+        cdef uint64_t db = <uint64_t> draw_base
+        cdef bint no_values = values is None
+        cdef int rc
+        with nogil:
+            rc = dist_gibbs_sample_rows(
+                self.ptr, rows, NULL if no_values else ptrs, mask_p, outs,
+                <uint32_t *> group.data, seed_state, db)
+        free(ptrs)
+        free(outs)
+        check(rc)
+        cols = []
+        for i in range(n):
+            s = self.shareds[i]
+            w = outw[i][:rows]
+            cols.append(w.view(np.float32) if s.c.kind == DIST_NICH else w)
+        return cols, group[:rows]
 
     def group_count(self):
         return checked_size(dist_gibbs_group_count(self.ptr))

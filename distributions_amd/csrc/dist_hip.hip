@@ -5161,6 +5161,94 @@ struct Gibbs {
                          + std::to_string(bad & 0xFF));
     }
 
+    // Whole rows and missing cells drawn from the mixture (kernels_sample.h)
+    DeviceBuf<float> sample_lik;      // [K + 1]: the nothing-observed instance
+    DeviceBuf<float> sample_w[kMaxF]; // DPD betas
+    DeviceBuf<unsigned long long> sample_bad;
+    void sample_rows(size_t n, const uint32_t * const * values_dev,
+                     const uint32_t * observed_dev, uint32_t * const * out_dev,
+                     uint32_t * group_dev, uint32_t seed_state,
+                     uint64_t draw_base) {
+        // the caches it reads are the frozen state's only between batches
+        DIST_REQUIRE(!batch_open, "batch open");
+        ex.require_whole("sample_rows");
+        if (n == 0) return;
+        DIST_REQUIRE(out_dev != nullptr || F() == 0, "null argument");
+        for (int f = 0; f < F(); ++f)
+            DIST_REQUIRE(out_dev[f] != nullptr, "null output column");
+        upload_maps();
+        const size_t step = std::min(n, (size_t)opt.predict_chunk);
+        ensure_pow_tables(step);
+        SweepParams P = params(0, 0, seed_state, draw_base);
+        prepare_base(P);
+        const size_t Kn = (size_t)K();
+        predict_prior.reserve(grow_capacity(Kn), 0);
+        LAUNCH(k_predict_prior, Kn, P, predict_prior.p);
+        const bool uncond = observed_dev == nullptr;
+        if (uncond) {
+            // one exponential per group, not per (row, group)
+            sample_lik.reserve(grow_capacity(Kn + 1), 0);
+            LAUNCH1(k_sample_prior_lik, (int)Kn, predict_prior.p,
+                    sample_lik.p);
+        }
+        SampleArgs A;
+        memset(&A, 0, sizeof(A));
+        for (int f = 0; f < F(); ++f) {
+            const Slave & sl = *feats[f];
+            if (sl.sh.kind == DIST_DPD) {
+                sample_w[f].upload(sl.betas.data(), (size_t)sl.sh.dim);
+                A.w[f] = sample_w[f].p;
+            } else if (sl.sh.kind == DIST_DD) {
+                A.w[f] = sl.prior.p;   // the alphas
+            }
+        }
+        sample_bad.reserve(2, 0);
+        HIP_CHECK(hipMemsetAsync(sample_bad.p, 0xFF,
+                                 2 * sizeof(unsigned long long), stream()));
+        A.prior = predict_prior.p;
+        A.lik = sample_lik.p;
+        A.p2g = d_p2g_ptr;
+        A.seed_state = seed_state;
+        A.bad = sample_bad.p;
+        for (size_t c0 = 0; c0 < n; c0 += step) {
+            const size_t c1 = std::min(n, c0 + step);
+            for (int f = 0; f < F(); ++f) {
+                P.values[f] = !uncond && values_dev && values_dev[f]
+                                  ? values_dev[f] + c0 : nullptr;
+                A.out[f] = out_dev[f] + c0;
+            }
+            P.row_begin = 0;
+            P.row_end = c1 - c0;
+            // row q draws its group with engine step draw_base + q + 1 of
+            // seed_state, whatever the chunking (the batch's own convention)
+            P.seed_batch = lcg_jump(seed_state, draw_base + c0 + 1ull);
+            A.observed = uncond ? nullptr : observed_dev + c0;
+            A.group = group_dev ? group_dev + c0 : nullptr;
+            A.row0 = (unsigned long long)(draw_base + c0);
+            A.q0 = (unsigned long long)c0;
+            if (uncond) {
+                hipLaunchKernelGGL(k_sample_rows<true>, grid_for(P.row_end),
+                                   dim3(kBlock), 0, stream(), P, A);
+            } else {
+                hipLaunchKernelGGL(k_sample_rows<false>, grid_for(P.row_end),
+                                   dim3(kBlock), 0, stream(), P, A);
+            }
+            HIP_CHECK(hipGetLastError());
+        }
+        unsigned long long bad[2] = {0, 0};
+        sample_bad.download(bad, 2);   // (waits for the work)
+        DIST_REQUIRE(bad[0] == ~0ull,
+                     "sample_rows: observed value outside its feature's "
+                     "domain (or in a column that was not given) at row "
+                         + std::to_string(bad[0] >> 8) + ", feature "
+                         + std::to_string(bad[0] & 0xFF));
+        DIST_REQUIRE(bad[1] == ~0ull,
+                     "sample_rows: a cell's bounded draw ran out of tries "
+                     "(NaN or degenerate hyper-parameters?) at row "
+                         + std::to_string(bad[1] >> 8) + ", feature "
+                         + std::to_string(bad[1] & 0xFF));
+    }
+
     // ---- the ranks' loop (dist_gibbs_sweep_sharded; the caller comes in by
     // GibbsRef::open(): a run the last pass left open may go on) ------------
     void sweep_sharded(dist_comm_t * c, size_t n_batches, size_t batch_rows,
@@ -6130,6 +6218,35 @@ int dist_group_score_value(const dist_shared_t * sh, const uint32_t * group,
     });
 }
 
+int dist_group_sample_value(const dist_shared_t * sh, const uint32_t * group,
+                            uint32_t seed_state, uint64_t row_first, size_t n,
+                            int feature, uint32_t * words_out) {
+    return guarded([&] {
+        check_shared(*sh);
+        DIST_REQUIRE(group != nullptr && (words_out != nullptr || n == 0),
+                     "null argument");
+        DIST_REQUIRE(feature >= 0 && feature < 255, "bad feature index");
+        SampleShared view;
+        view.kind = sh->kind;
+        view.dim = sh->dim;
+        for (int i = 0; i < 4; ++i) view.p[i] = sh->p[i];
+        view.w = sh->kind == DIST_DD ? sh->alphas
+                 : sh->kind == DIST_DPD ? sh->betas : nullptr;
+        const Stats st = group_to_stats(*sh, group);
+        const int32_t * cnt = reinterpret_cast<const int32_t *>(group + 1);
+        for (size_t i = 0; i < n; ++i) {
+            bool exhausted = false;
+            words_out[i] = sample_cell_word(sh->kind, view, st, cnt,
+                                            seed_state, row_first + i,
+                                            feature, &exhausted);
+            DIST_REQUIRE(!exhausted,
+                         "sample_value: a bounded draw ran out of tries "
+                         "(NaN or degenerate hyper-parameters?) at row "
+                             + std::to_string(row_first + i));
+        }
+    });
+}
+
 size_t dist_scorer_words(const dist_shared_t * sh) {
     return is_cat(sh->kind) ? (size_t)sh->dim + 1 : 4;
 }
@@ -6664,6 +6781,51 @@ int dist_gibbs_predict_feature(dist_gibbs_t * g, size_t n_rows,
         if (joint_out) joint.download(joint_out, n_rows * C);
         if (base_out) base.download(base_out, n_rows);
         if (choice_out) choice.download(choice_out, n_rows);
+    });
+}
+int dist_gibbs_sample_rows_dev(dist_gibbs_t * g, size_t n_rows,
+                               const uint32_t * const * values_dev,
+                               const uint32_t * observed_dev,
+                               uint32_t * const * out_dev,
+                               uint32_t * group_dev, uint32_t seed_state,
+                               uint64_t draw_base) {
+    return guarded([&] {
+        g->impl.read()->sample_rows(n_rows, values_dev, observed_dev, out_dev,
+                                    group_dev, seed_state, draw_base);
+    });
+}
+int dist_gibbs_sample_rows(dist_gibbs_t * g, size_t n_rows,
+                           const uint32_t * const * values,
+                           const uint32_t * observed, uint32_t * const * out,
+                           uint32_t * group_out, uint32_t seed_state,
+                           uint64_t draw_base) {
+    return guarded([&] {
+        Gibbs * e = g->impl.read();
+        const int F = e->F();
+        DIST_REQUIRE(out != nullptr || F == 0 || n_rows == 0, "null argument");
+        // one device column per feature: the observed words go up, the
+        // completed column comes back (completion in place)
+        std::vector<DeviceBuf<uint32_t>> cols((size_t)F);
+        std::vector<const uint32_t *> in((size_t)F, nullptr);
+        std::vector<uint32_t *> outp((size_t)F, nullptr);
+        for (int f = 0; f < F && n_rows; ++f) {
+            DIST_REQUIRE(out[f] != nullptr, "null output column");
+            if (observed && values && values[f]) {
+                cols[f].upload(values[f], n_rows);
+                in[f] = cols[f].p;
+            } else {
+                cols[f].reserve(n_rows, 0);
+            }
+            outp[f] = cols[f].p;
+        }
+        DeviceBuf<uint32_t> mask, group;
+        if (observed && n_rows) mask.upload(observed, n_rows);
+        if (group_out) group.reserve(std::max<size_t>(n_rows, 1), 0);
+        e->sample_rows(n_rows, in.data(), observed ? mask.p : nullptr,
+                       outp.data(), group.p, seed_state, draw_base);
+        for (int f = 0; f < F && n_rows; ++f)
+            cols[f].download(out[f], n_rows);
+        if (group_out) group.download(group_out, n_rows);
     });
 }
 size_t dist_gibbs_group_count(const dist_gibbs_t * g) {

@@ -238,6 +238,67 @@ class Gibbs(object):
             0 if staged else _core.PREDICT_FEATURE_RECOMPUTE)
         return joint, base, choice
 
+    def sample_rows(self, n=None, values=None, observed=None, seed=0,
+                    draw_base=0):
+        """Rows that are NOT in the table, drawn from the mixture: synthetic
+        rows, or the joint completion of rows with holes.
+        observed: one uint32 mask per row, bit f set when feature f of the
+        row is observed (required when `values` is given); None: nothing is
+        observed and `n` rows are drawn.  values: one host array per feature
+        (None for a feature no row observes; words in unobserved cells are
+        never read).  -> (columns, groups): per row q a group (a global id)
+        drawn from the clustering model's score_value folded with the
+        observed features' (mixture.hpp:416-425) with engine step
+        draw_base + q + 1 of `seed` -- predict(mode="sample")'s group when
+        everything is observed -- and then EVERY unobserved cell drawn from
+        that one group's posterior predictive (Group::sample_value), so the
+        cells of a row fit together; observed cells come back as given.
+        columns[f] is float32 for NormalInverseChiSq, uint32 otherwise
+        (0xFFFFFFFF: a DirichletProcessDiscrete value outside the table).
+        Cell (q, f) depends on (seed, draw_base + q, f) alone: calls over
+        disjoint draw_base ranges are independent.  Nothing in the engine
+        changes."""
+        return self.core.sample_rows(n, None if values is None
+                                     else list(values), observed,
+                                     _core.rng_seed(seed), draw_base)
+
+    def sample_rows_torch(self, n=None, values=None, observed=None, seed=0,
+                          draw_base=0, out=None):
+        """sample_rows for device tensors (values: one 4-byte-per-row CUDA
+        tensor per feature or None; observed a CUDA int32 tensor or None):
+        the results are tensors on the same device (the current one when
+        nothing is given) and nothing is staged through the host.  out: the
+        tensors to fill, one per feature; out[f] may be values[f] itself,
+        which completes the rows in place (only unobserved cells are
+        written).  -> (columns, groups)"""
+        import torch
+        if values is not None and observed is None:
+            raise RuntimeError("sample_rows: values need an observed mask")
+        if observed is not None:
+            observed = observed.contiguous()
+            n = int(observed.numel())
+            dev = observed.device
+        else:
+            values = None
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if values is not None:
+            values = [None if v is None else v.contiguous() for v in values]
+        if out is None:
+            out = [torch.empty(n, dtype=torch.float32
+                               if s.kind == _core.KIND_NICH else torch.int32,
+                               device=dev) for s in self.shareds]
+        groups = torch.empty(n, dtype=torch.int32, device=dev)
+        # (the library works on its own stream: what filled the tensors on
+        # torch's must be done)
+        torch.cuda.current_stream(dev).synchronize()
+        self.core.sample_rows_dev(
+            None if values is None
+            else [0 if v is None else int(v.data_ptr()) for v in values], n,
+            0 if observed is None else int(observed.data_ptr()),
+            [int(o.data_ptr()) for o in out], int(groups.data_ptr()),
+            _core.rng_seed(seed), draw_base)
+        return out, groups
+
     # -- hyper-parameters ---------------------------------------------------
     # The step the reference alternates with assignment sweeps
     # (mixture.hpp:427-438, then sample_from_scores and init()), on the
@@ -556,6 +617,19 @@ class ShardedGibbs(object):
             list(values), target, candidates, observed,
             Gibbs._PREDICT_MODES[mode], seed_state, draw_base,
             0 if staged else _core.PREDICT_FEATURE_RECOMPUTE)
+
+    def sample_rows(self, n=None, values=None, observed=None, seed_state=0,
+                    draw_base=0):
+        """Each rank draws ITS rows from the common state (as
+        Gibbs.sample_rows; seed_state is a raw engine state).  Cell (q, f)
+        and row q's group depend on (seed_state, draw_base + q) alone, so
+        ranks that share a seed_state MUST be given disjoint
+        [draw_base, draw_base + n) ranges, or they draw the same rows.  A
+        value-partitioned rank gathers its cells first."""
+        self._whole()
+        return self.backend.sample_rows(n, None if values is None
+                                        else list(values), observed,
+                                        seed_state, draw_base)
 
     def score_data(self):
         self._whole()

@@ -244,6 +244,22 @@ int dist_group_score_value(const dist_shared_t * shared,
                            float * out);
 int dist_group_score_data(const dist_shared_t * shared, const uint32_t * group,
                           float * out);
+/* Group::sample_value (dd.hpp:188-199, bb.hpp:154-160, gp.hpp:166-172,
+ * nich.hpp:204-210, bnb.hpp:168-174, dpd.hpp:275-305): n draws from the
+ * group's posterior predictive -- the law whose log density
+ * dist_group_score_value returns; for BetaNegativeBinomial that score plus
+ * log C(x + r - 1, x), which the reference's score leaves out and a sampler
+ * cannot.  words_out[i] is the draw of cell (row_first + i, feature): the
+ * counter-based stream keyed by (seed_state, row, feature) and the binary64
+ * arithmetic of csrc/sample.h, the very inline function the kernels of
+ * dist_gibbs_sample_rows call.  Counts, or float bits for NormalInverseChiSq;
+ * DIST_DPD_OTHER where a DirichletProcessDiscrete draw leaves the table.  Host
+ * only, needs no device.  Fails when a bounded rejection loop runs out of
+ * tries (NaN hyper-parameters). */
+int dist_group_sample_value(const dist_shared_t * shared,
+                            const uint32_t * group, uint32_t seed_state,
+                            uint64_t row_first, size_t n, int feature,
+                            uint32_t * words_out);
 /* Model::Scorer (dd.hpp:222-245, bb.hpp:185-205, gp.hpp:198-217,
  * nich.hpp:239-259, bnb.hpp:195-223, dpd.hpp:309-341): init caches what eval
  * needs of ONE group's statistics, eval scores a value from the cache -- the
@@ -658,6 +674,52 @@ int dist_gibbs_predict_feature(dist_gibbs_t * g, size_t n_rows,
                                float * base_out, uint32_t * choice_out,
                                int mode, uint32_t seed_state,
                                uint64_t draw_base, unsigned flags);
+
+/* Held-out rows: whole rows and missing cells drawn from the mixture.  Per
+ * query row q with mask observed[q] (bit f set: feature f of row q is
+ * observed; bits >= F are ignored; observed == NULL: nothing is observed):
+ *   scores[k], k in [0, dist_gibbs_group_count), empty groups included: the
+ *     driver's score_value as in dist_gibbs_predict, then in feature order
+ *     (mixture.hpp:416-425) every OBSERVED feature's score_value with the
+ *     row's value -- dist_gibbs_predict_feature's `base` fold;
+ *   group[q], a global id: sample_from_scores_overwrite (random.hpp:361-366)
+ *     over them with engine step draw_base + q + 1 of seed_state.  With every
+ *     feature observed it is dist_gibbs_predict's mode-0 group, bit for bit;
+ *   cell (q, f) of every feature that is NOT observed: a draw from group[q]'s
+ *     posterior predictive, Group::sample_value (dd.hpp:188-199,
+ *     bb.hpp:154-160, gp.hpp:166-172, nich.hpp:204-210, bnb.hpp:168-174,
+ *     dpd.hpp:275-305) as dist_group_sample_value defines it, keyed by
+ *     (seed_state, draw_base + q, f); an empty group gives prior-predictive
+ *     cells.  Observed cells are returned as given.
+ * Results do not depend on chunking or launch geometry; calls over disjoint
+ * [draw_base, draw_base + n_rows) ranges draw disjoint streams.
+ * values: F columns of n_rows words, NULL altogether when observed is NULL; a
+ * single column may be NULL for a feature no row observes.  Words in
+ * unobserved cells are never read.  An observed DirichletDiscrete value >= dim
+ * or BetaBernoulli value > 1 (or an observed cell of a NULL column) fails the
+ * call naming the first such row and its feature; a DirichletProcessDiscrete
+ * value the table does not hold scores as OTHER.  out: F columns of n_rows
+ * words; out[f] may be values[f] (completion in place: only the unobserved
+ * cells are written).  group may be NULL.  A cell whose bounded rejection loop
+ * ran out of tries (NaN hyper-parameters) fails the call naming the first.
+ * A pure reader under the rules of dist_gibbs_predict: nothing in the engine
+ * changes, refused while a batch is open and on a value-partitioned rank whose
+ * cells are stale; n_rows == 0 does nothing; at most "debug.predict_chunk"
+ * rows per launch.  Returns when the work is done.
+ * _dev: values_dev and out_dev are host arrays of F device pointers;
+ * observed_dev and group_dev are device pointers.  The host form stages,
+ * calls and downloads. */
+int dist_gibbs_sample_rows_dev(dist_gibbs_t * g, size_t n_rows,
+                               const uint32_t * const * values_dev,
+                               const uint32_t * observed_dev,
+                               uint32_t * const * out_dev,
+                               uint32_t * group_dev, uint32_t seed_state,
+                               uint64_t draw_base);
+int dist_gibbs_sample_rows(dist_gibbs_t * g, size_t n_rows,
+                           const uint32_t * const * values,
+                           const uint32_t * observed, uint32_t * const * out,
+                           uint32_t * group_out, uint32_t seed_state,
+                           uint64_t draw_base);
 
 size_t dist_gibbs_group_count(const dist_gibbs_t * g);     /* counts().size() */
 size_t dist_gibbs_row_count(const dist_gibbs_t * g);
