@@ -234,6 +234,16 @@ cdef extern from "distributions_hip.h" nogil:
     int dist_gibbs_predict(dist_gibbs_t *, size_t, const uint32_t * const *,
                            float *, uint32_t *, int, uint32_t, uint64_t,
                            float *)
+    int dist_gibbs_predict_many_dev(dist_gibbs_t * const *, size_t, size_t,
+                                    const uint32_t * const *, float *,
+                                    uint32_t *, uint32_t *, int, uint32_t,
+                                    uint32_t, uint64_t, float *, size_t,
+                                    float *, unsigned) nogil
+    int dist_gibbs_predict_many(dist_gibbs_t * const *, size_t, size_t,
+                                const uint32_t * const *, float *,
+                                uint32_t *, uint32_t *, int, uint32_t,
+                                uint32_t, uint64_t, float *, size_t, float *,
+                                unsigned) nogil
     int dist_gibbs_predict_feature_dev(dist_gibbs_t *, size_t,
                                        const uint32_t * const *,
                                        const uint32_t *, int,
@@ -303,6 +313,7 @@ cdef extern from "distributions_hip.h" nogil:
 
 
 PREDICT_FEATURE_RECOMPUTE = 1   # DIST_PREDICT_FEATURE_RECOMPUTE
+PREDICT_MANY_DRAW_ALL = 1       # DIST_PREDICT_MANY_DRAW_ALL
 KIND_DD = DIST_DD
 KIND_BB = DIST_BB
 KIND_GP = DIST_GP
@@ -1913,3 +1924,128 @@ def sweep_sequential_many(engines, size_t row_begin, size_t row_end,
         free(ptrs)
     check(rc)
     return st
+
+
+cdef dist_gibbs_t ** _engine_ptrs(engines) except NULL:
+    """a malloc'ed array of the engines' handles (None: a null handle)"""
+    cdef size_t m = len(engines)
+    cdef dist_gibbs_t ** ptrs = <dist_gibbs_t **> malloc(
+        (m if m else 1) * sizeof(dist_gibbs_t *))
+    cdef size_t i
+    cdef GibbsEngine e
+    for i in range(m):
+        if engines[i] is None:
+            ptrs[i] = NULL
+            continue
+        try:
+            e = engines[i]
+        except TypeError:
+            free(ptrs)
+            raise
+        ptrs[i] = e.ptr
+    return ptrs
+
+
+def predict_many_dev(engines, value_ptrs, size_t n_rows, size_t logp_ptr,
+                     size_t member_ptr, size_t group_ptr, int mode,
+                     uint32_t seed_state, uint32_t member_seed_state,
+                     draw_base=0, size_t members_logp_ptr=0,
+                     size_t members_ld=0, bint prior_totals=True,
+                     unsigned flags=0):
+    """Held-out rows against M engines (dist_gibbs_predict_many_dev):
+    engines = GibbsEngine objects, value_ptrs device addresses of one column
+    of n_rows words per feature, the other pointers device addresses or 0.
+    -> the engines' prior totals (numpy float32), or None"""
+    cdef size_t m = len(engines)
+    cdef size_t nf = len(value_ptrs)
+    cdef const uint32_t ** cols = <const uint32_t **> malloc(
+        sizeof(void *) * (nf + 1))
+    cdef size_t i
+    cdef size_t addr
+    for i in range(nf):
+        addr = value_ptrs[i]
+        cols[i] = <const uint32_t *> addr
+    cdef cnp.ndarray[cnp.float32_t, ndim=1] totals = np.zeros(
+        m if m else 1, np.float32)
+    cdef float * tp = <float *> totals.data if prior_totals else NULL
+    cdef uint64_t db = <uint64_t> draw_base
+    cdef dist_gibbs_t ** ptrs
+    cdef int rc
+    try:
+        ptrs = _engine_ptrs(engines)
+    except Exception:
+        free(cols)
+        raise
+    with nogil:
+        rc = dist_gibbs_predict_many_dev(
+            <dist_gibbs_t * const *> ptrs, m, n_rows, cols,
+            <float *> logp_ptr, <uint32_t *> member_ptr,
+            <uint32_t *> group_ptr, mode, seed_state, member_seed_state, db,
+            <float *> members_logp_ptr, members_ld, tp, flags)
+    free(ptrs)
+    free(cols)
+    check(rc)
+    return totals[:m].copy() if prior_totals else None
+
+
+def predict_many(engines, values, mode, uint32_t seed_state,
+                 uint32_t member_seed_state, draw_base=0, bint members=False,
+                 unsigned flags=0):
+    """Held-out rows against M engines from host arrays
+    (dist_gibbs_predict_many): values is one array per feature; mode 0 draws,
+    1 takes the first maximum, None leaves members and groups out.
+    -> (logp, members or None, groups or None, members_logp [M, n] or None,
+    prior_totals [M])"""
+    cdef size_t m = len(engines)
+    if m == 0 or engines[0] is None:
+        raise RuntimeError("predict_many: no engine" if m == 0
+                           else "null engine")
+    cdef GibbsEngine first = engines[0]
+    cdef int n = len(first.shareds)
+    if len(values) != n:
+        raise RuntimeError("one value column per feature")
+    cdef const uint32_t ** cols = <const uint32_t **> malloc(
+        sizeof(void *) * (n + 1))
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] w
+    cdef SharedParams s
+    words = []
+    cdef int i
+    cdef size_t rows = 0
+    for i in range(n):
+        s = first.shareds[i]
+        w = value_words(s.c.kind, values[i])
+        if i and <size_t> w.shape[0] != rows:
+            free(cols)
+            raise RuntimeError("feature columns differ in length")
+        rows = w.shape[0]
+        words.append(w)
+        cols[i] = <const uint32_t *> w.data
+    cdef cnp.ndarray[cnp.float32_t, ndim=1] logp = np.zeros(rows, np.float32)
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] member = np.zeros(rows, np.uint32)
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] group = np.zeros(rows, np.uint32)
+    cdef cnp.ndarray[cnp.float32_t, ndim=2] planes = np.zeros(
+        (m if members else 1, rows if members else 1), np.float32)
+    cdef cnp.ndarray[cnp.float32_t, ndim=1] totals = np.zeros(m, np.float32)
+    cdef uint32_t * mp = NULL if mode is None else <uint32_t *> member.data
+    cdef uint32_t * gp = NULL if mode is None else <uint32_t *> group.data
+    cdef float * pp = <float *> planes.data if members else NULL
+    cdef int md = 0 if mode is None else mode
+    cdef uint64_t db = <uint64_t> draw_base
+    cdef dist_gibbs_t ** ptrs
+    cdef int rc
+    try:
+        ptrs = _engine_ptrs(engines)
+    except Exception:
+        free(cols)
+        raise
+    with nogil:
+        rc = dist_gibbs_predict_many(
+            <dist_gibbs_t * const *> ptrs, m, rows, cols,
+            <float *> logp.data, mp, gp, md, seed_state, member_seed_state,
+            db, pp, rows, <float *> totals.data, flags)
+    free(ptrs)
+    free(cols)
+    check(rc)
+    return (logp, None if mode is None else member,
+            None if mode is None else group, planes if members else None,
+            totals)

@@ -5000,6 +5000,41 @@ struct Gibbs {
                          + std::to_string(bad & 0xFF));
     }
 
+    // The predictive averaged over M engines (kernels_ensemble.h,
+    // predict_many below): the first engine holds the call's buffers
+    DeviceBuf<PredictMember> many_args;
+    DeviceBuf<float> many_w;           // [M][chunk] unless the caller's
+    DeviceBuf<uint32_t> many_groups;   // [M][chunk], draw-all form
+    DeviceBuf<uint32_t> many_member;   // [chunk] when only the group is asked
+    DeviceBuf<float> many_totals;      // [M]
+    // the most words of many_w and of many_groups: each stays under 1 GiB
+    static constexpr size_t kManyScratchWords = ((size_t)1 << 28) - 1;
+    struct PredictManyLaunch {
+        const PredictMember * args;
+        unsigned m;
+        size_t rows;
+        template <int KA, int KB, int NF>
+        void run() {
+            hipLaunchKernelGGL((k_predict_many<KA, KB, NF>),
+                               dim3(grid_for(rows).x, m), dim3(kBlock), 0,
+                               stream(), args);
+            HIP_CHECK(hipGetLastError());
+        }
+    };
+    struct PredictPickLaunch {
+        const PredictMember * args;
+        unsigned m;
+        size_t rows;
+        const uint32_t * member;
+        template <int KA, int KB, int NF>
+        void run() {
+            const int per = predict_many_pick_rows(m);
+            launch_lds<&k_predict_many_pick<KA, KB, NF>>(
+                dim3((unsigned)((rows + per - 1) / per), m), dim3(kBlock),
+                predict_many_pick_lds(per), args, member, per);
+        }
+    };
+
     // One feature's predictive given the others (kernels_feature.h)
     DeviceBuf<uint32_t> feature_cand;
     DeviceBuf<float> feature_joint;   // [chunk][C]: choice without joint
@@ -5519,6 +5554,16 @@ struct Gibbs {
     static void sweep_sequential_many(dist_gibbs_t * const * engines, size_t m,
                                       size_t row_begin, size_t row_end,
                                       uint32_t * rng_states);
+    // held-out rows against M engines: the predictive averaged over them
+    // (kernels_ensemble.h; defined behind GibbsRef as well)
+    static void predict_many(dist_gibbs_t * const * engines, size_t m,
+                             size_t n, const uint32_t * const * values_dev,
+                             float * logp_dev, uint32_t * member_dev,
+                             uint32_t * group_dev, int mode,
+                             uint32_t seed_state, uint32_t member_seed_state,
+                             uint64_t draw_base, float * members_logp_dev,
+                             size_t members_ld, float * prior_totals_out,
+                             unsigned flags);
 };
 
 }  // namespace dist
@@ -5642,6 +5687,171 @@ void dist::Gibbs::sweep_sequential_many(dist_gibbs_t * const * engines,
         todo.swap(again);
     }
     dist::sync();
+}
+
+void dist::Gibbs::predict_many(dist_gibbs_t * const * engines, size_t m,
+                               size_t n, const uint32_t * const * values_dev,
+                               float * logp_dev, uint32_t * member_dev,
+                               uint32_t * group_dev, int mode,
+                               uint32_t seed_state,
+                               uint32_t member_seed_state, uint64_t draw_base,
+                               float * members_logp_dev, size_t members_ld,
+                               float * prior_totals_out, unsigned flags) {
+    DIST_REQUIRE(mode == 0 || mode == 1,
+                 "predict_many: mode is 0 (draw) or 1 (first maximum)");
+    DIST_REQUIRE((flags & ~(unsigned)DIST_PREDICT_MANY_DRAW_ALL) == 0,
+                 "predict_many: unknown flag");
+    DIST_REQUIRE(m == 0 || engines, "null argument");
+    if (!m) return;
+    DIST_REQUIRE(m <= 65535, "predict_many: at most 65535 engines");
+    std::vector<Gibbs *> e(m);
+    for (size_t i = 0; i < m; ++i) {
+        DIST_REQUIRE(engines[i], "null engine");
+        e[i] = engines[i]->impl.read();   // (settles, stays resumable)
+        for (size_t j = 0; j < i; ++j)
+            DIST_REQUIRE(e[j] != e[i], "the same engine twice");
+        DIST_REQUIRE(e[i]->F() == e[0]->F(), "engines of one feature list");
+        for (int f = 0; f < e[0]->F(); ++f)
+            DIST_REQUIRE(e[i]->feats[f]->sh.kind == e[0]->feats[f]->sh.kind
+                             && e[i]->feats[f]->sh.dim
+                                    == e[0]->feats[f]->sh.dim,
+                         "engines of one feature list");
+        DIST_REQUIRE(e[i]->cluster == e[0]->cluster,
+                     "engines of one clustering model");
+        // the caches it reads are the frozen state's only between batches
+        DIST_REQUIRE(!e[i]->batch_open, "batch open");
+        e[i]->ex.require_whole("predict_many");
+    }
+    if (!n) return;
+    Gibbs & first = *e[0];
+    const int F = first.F();
+    DIST_REQUIRE(values_dev != nullptr || F == 0, "null argument");
+    for (int f = 0; f < F; ++f)
+        DIST_REQUIRE(values_dev[f] != nullptr, "null value column");
+    DIST_REQUIRE(!members_logp_dev || members_ld >= n,
+                 "predict_many: members_ld is less than the row count");
+    const bool draw_all =
+        (flags & DIST_PREDICT_MANY_DRAW_ALL) != 0 && group_dev != nullptr;
+    const bool le = first.cluster == 1;
+    const bool want_totals = le || prior_totals_out != nullptr;
+    size_t step = std::min(n, (size_t)first.opt.predict_chunk);
+    step = std::min(step, std::max<size_t>(1, kManyScratchWords / m));
+
+    first.many_args.reserve(grow_capacity(m), 0);
+    if (!members_logp_dev) first.many_w.reserve(m * step, 0);
+    if (draw_all) first.many_groups.reserve(m * step, 0);
+    if (group_dev && !member_dev) first.many_member.reserve(step, 0);
+    if (want_totals) first.many_totals.reserve(grow_capacity(m), 0);
+    first.predict_bad.reserve(1, 0);
+    HIP_CHECK(hipMemsetAsync(first.predict_bad.p, 0xFF,
+                             sizeof(unsigned long long), stream()));
+    first.ensure_pow_tables(step);
+    std::vector<PredictMember> args(m);
+    memset(args.data(), 0, m * sizeof(PredictMember));
+    size_t k_max = 0;
+    for (size_t i = 0; i < m; ++i) {
+        Gibbs & g = *e[i];
+        g.upload_maps();
+        g.ensure_pow_tables(step);
+        PredictMember & pm = args[i];
+        pm.P = g.params(0, 0, seed_state, draw_base);
+        g.prepare_base(pm.P);
+        const size_t Kn = (size_t)g.K();
+        k_max = std::max(k_max, Kn);
+        g.predict_prior.reserve(grow_capacity(Kn), 0);
+        pm.prior = g.predict_prior.p;
+        pm.total = want_totals ? first.many_totals.p + i : nullptr;
+        pm.sub = le ? pm.total : nullptr;
+    }
+    uint32_t * const member =
+        member_dev ? member_dev
+                   : (group_dev ? first.many_member.p : nullptr);
+    for (size_t c0 = 0; c0 < n; c0 += step) {
+        const size_t c1 = std::min(n, c0 + step);
+        const size_t rows = c1 - c0;
+        float * const w = members_logp_dev ? members_logp_dev + c0
+                                           : first.many_w.p;
+        const size_t ld = members_logp_dev ? members_ld : step;
+        for (size_t i = 0; i < m; ++i) {
+            PredictMember & pm = args[i];
+            for (int f = 0; f < F; ++f) pm.P.values[f] = values_dev[f] + c0;
+            pm.P.row_begin = 0;
+            pm.P.row_end = rows;
+            // row q draws with engine step draw_base + q + 1 of seed_state,
+            // whatever the chunking (the batch's own convention)
+            pm.P.seed_batch = lcg_jump(seed_state, draw_base + c0 + 1ull);
+            pm.A.prior = pm.prior;
+            pm.A.p2g = e[i]->d_p2g_ptr;
+            pm.A.logp = w + i * ld;
+            pm.A.group = draw_all ? first.many_groups.p + i * step : nullptr;
+            pm.A.mode = mode;
+            pm.A.q0 = (unsigned long long)c0;
+            pm.A.bad = first.predict_bad.p;
+            pm.B = pm.A;
+            pm.B.logp = nullptr;
+            pm.B.group = group_dev ? group_dev + c0 : nullptr;
+        }
+        first.many_args.upload(args.data(), m);
+        if (c0 == 0) {
+            hipLaunchKernelGGL(k_predict_prior_many,
+                               dim3(grid_for(k_max).x, (unsigned)m),
+                               dim3(kBlock), 0, stream(), first.many_args.p);
+            HIP_CHECK(hipGetLastError());
+            if (want_totals) {
+                hipLaunchKernelGGL(k_predict_prior_totals,
+                                   grid_for(m, 64), dim3(64), 0, stream(),
+                                   first.many_args.p, (int)m);
+                HIP_CHECK(hipGetLastError());
+            }
+        }
+        PredictManyLaunch A{first.many_args.p, (unsigned)m, rows};
+        first.dispatch(A);
+        if (logp_dev || member) {
+            EnsembleFold fold;
+            memset(&fold, 0, sizeof(fold));
+            fold.w = w;
+            fold.ld = ld;
+            fold.m = (int)m;
+            fold.items = rows;
+            fold.logp = logp_dev ? logp_dev + c0 : nullptr;
+            fold.member = member ? (member_dev ? member + c0 : member)
+                                 : nullptr;
+            fold.mode = mode;
+            fold.seed_batch =
+                lcg_jump(member_seed_state, draw_base + c0 + 1ull);
+            fold.pow_lo = first.pow_lo.p;
+            fold.pow_hi = first.pow_hi.p;
+            if (draw_all) {
+                fold.groups = first.many_groups.p;
+                fold.groups_ld = step;
+                fold.group = group_dev + c0;
+            }
+            LAUNCH(k_ensemble_fold, rows, fold);
+            if (group_dev && !draw_all) {
+                PredictPickLaunch B{first.many_args.p, (unsigned)m, rows,
+                                    fold.member};
+                first.dispatch(B);
+            }
+        }
+    }
+    // the call's one wait: the word of the bad values and the prior totals
+    char * pinned = chain_pinned(64 + m * sizeof(float));
+    HIP_CHECK(hipMemcpyAsync(pinned, first.predict_bad.p,
+                             sizeof(unsigned long long),
+                             hipMemcpyDeviceToHost, stream()));
+    if (prior_totals_out)
+        HIP_CHECK(hipMemcpyAsync(pinned + 64, first.many_totals.p,
+                                 m * sizeof(float), hipMemcpyDeviceToHost,
+                                 stream()));
+    HIP_CHECK(hipStreamSynchronize(stream()));
+    unsigned long long bad = 0;
+    memcpy(&bad, pinned, sizeof(bad));
+    if (prior_totals_out)
+        memcpy(prior_totals_out, pinned + 64, m * sizeof(float));
+    DIST_REQUIRE(bad == ~0ull,
+                 "predict_many: value outside its feature's domain at row "
+                     + std::to_string(bad >> 8) + ", feature "
+                     + std::to_string(bad & 0xFF));
 }
 
 extern "C" {
@@ -6722,6 +6932,73 @@ int dist_gibbs_predict(dist_gibbs_t * g, size_t n_rows,
                    draw_base, prior_total_out);
         if (logp_out) logp.download(logp_out, n_rows);
         if (group_out) group.download(group_out, n_rows);
+    });
+}
+int dist_gibbs_predict_many_dev(dist_gibbs_t * const * engines, size_t m,
+                                size_t n_rows,
+                                const uint32_t * const * values_dev,
+                                float * logp_dev, uint32_t * member_dev,
+                                uint32_t * group_dev, int mode,
+                                uint32_t seed_state,
+                                uint32_t member_seed_state,
+                                uint64_t draw_base, float * members_logp_dev,
+                                size_t members_ld, float * prior_totals_out,
+                                unsigned flags) {
+    return guarded([&] {
+        Gibbs::predict_many(engines, m, n_rows, values_dev, logp_dev,
+                            member_dev, group_dev, mode, seed_state,
+                            member_seed_state, draw_base, members_logp_dev,
+                            members_ld, prior_totals_out, flags);
+    });
+}
+int dist_gibbs_predict_many(dist_gibbs_t * const * engines, size_t m,
+                            size_t n_rows, const uint32_t * const * values,
+                            float * logp_out, uint32_t * member_out,
+                            uint32_t * group_out, int mode,
+                            uint32_t seed_state, uint32_t member_seed_state,
+                            uint64_t draw_base, float * members_logp_out,
+                            size_t members_ld, float * prior_totals_out,
+                            unsigned flags) {
+    return guarded([&] {
+        DIST_REQUIRE(m == 0 || engines, "null argument");
+        std::vector<DeviceBuf<uint32_t>> cols;
+        std::vector<const uint32_t *> ptrs;
+        if (m && engines[0] && n_rows) {
+            const int F = engines[0]->impl.read()->F();
+            DIST_REQUIRE(values != nullptr || F == 0, "null argument");
+            cols.resize((size_t)F);
+            ptrs.resize((size_t)F);
+            for (int f = 0; f < F; ++f) {
+                DIST_REQUIRE(values[f] != nullptr, "null value column");
+                cols[f].upload(values[f], n_rows);
+                ptrs[f] = cols[f].p;
+            }
+        }
+        DIST_REQUIRE(!members_logp_out || members_ld >= n_rows,
+                     "predict_many: members_ld is less than the row count");
+        const size_t cells = std::max<size_t>(n_rows, 1);
+        DeviceBuf<float> logp, planes;
+        DeviceBuf<uint32_t> member, group;
+        if (logp_out) logp.reserve(cells, 0);
+        if (member_out) member.reserve(cells, 0);
+        if (group_out) group.reserve(cells, 0);
+        if (members_logp_out) planes.reserve(std::max<size_t>(m, 1) * cells, 0);
+        Gibbs::predict_many(engines, m, n_rows, ptrs.data(), logp.p, member.p,
+                            group.p, mode, seed_state, member_seed_state,
+                            draw_base, planes.p, n_rows, prior_totals_out,
+                            flags);
+        if (!m || !n_rows) return;
+        if (logp_out) logp.download(logp_out, n_rows);
+        if (member_out) member.download(member_out, n_rows);
+        if (group_out) group.download(group_out, n_rows);
+        if (members_logp_out) {
+            HIP_CHECK(hipMemcpy2DAsync(members_logp_out,
+                                       members_ld * sizeof(float), planes.p,
+                                       n_rows * sizeof(float),
+                                       n_rows * sizeof(float), m,
+                                       hipMemcpyDeviceToHost, stream()));
+            dist::sync();
+        }
     });
 }
 int dist_gibbs_predict_feature_dev(dist_gibbs_t * g, size_t n_rows,

@@ -115,11 +115,10 @@ struct PredictScorer {
     }
 };
 
-// One lane = one query row, groups in index order: 64 independent in-order
-// chains per wave, as in k_sweep_sample.  Scores are recomputed per pass.
-// P.values are the launch's query columns, P.row_begin = 0, P.row_end the
-// launch's row count, P.seed_batch the engine state one step before the
-// launch's first row's draw.
+// One lane = one query row; the body, shared with kernels_ensemble.h, is
+// kernels_predict_body.h.  P.values are the launch's query columns,
+// P.row_begin = 0, P.row_end the launch's row count, P.seed_batch the engine
+// state one step before the launch's first row's draw.
 template <int KIND0, int KIND1, int NF>
 __global__ __launch_bounds__(kBlock) void k_predict(SweepParams P,
                                                     PredictArgs A) {
@@ -127,57 +126,17 @@ __global__ __launch_bounds__(kBlock) void k_predict(SweepParams P,
     for (int i = threadIdx.x; i < 1024; i += kBlock)
         s_exp[i] = g_tables_dev.exp_table[i];
     __syncthreads();
-    const float ea = u2f(g_tables_dev.exp_ab[0]);
-    const float eb = u2f(g_tables_dev.exp_ab[1]);
-    const int K = P.K;
-    const bool draw = A.group != nullptr && A.mode == 0;
-
-    const size_t stride = (size_t)gridDim.x * kBlock;
-    const size_t n = P.row_end;
-    // whole waves iterate together so that the vote below sees every lane
-    const size_t n_round = (n + 63) / 64 * 64;
-    for (size_t item = (size_t)blockIdx.x * kBlock + threadIdx.x;
-         item < n_round; item += stride) {
-        const bool live = item < n;
-        const size_t q = live ? item : 0;
-        const PredictScorer<KIND0, KIND1, NF> ps(P, A, q, live);
-        // vector_max (vector_math.cc:74-83); the first index that attains it
-        float m = ps.at(0);
-        int arg = 0;
-#pragma unroll kSweepUnroll
-        for (int k = 1; k < K; ++k) {
-            const float s = ps.at(k);
-            arg = s > m ? k : arg;
-            m = s > m ? s : m;
-        }
-        int g2 = arg;
-        if (A.logp != nullptr || draw) {
-            float total = 0.f;
-#pragma unroll kSweepUnroll
-            for (int k = 0; k < K; ++k)
-                total += fast_exp_nonpos(ps.at(k) - m, s_exp, ea, eb);
-            if (live && A.logp != nullptr) A.logp[q] = fast_log(total) + m;
-            if (draw) {
-                // sample_from_likelihoods: the first index with t <= 0 is
-                // the number of steps after which t is still positive
-                float t = total * batch_row_unif01(P, q);
-                int steps = 0;
-                for (int k0 = 0; k0 < K; k0 += kSweepUnroll) {
-#pragma unroll
-                    for (int j = 0; j < kSweepUnroll; ++j) {
-                        const int k = k0 + j;
-                        if (k < K) {
-                            t -= fast_exp_nonpos(ps.at(k) - m, s_exp, ea, eb);
-                            steps += t > 0.f ? 1 : 0;
-                        }
-                    }
-                    if (!__any(live && t > 0.f)) break;
-                }
-                g2 = steps < K - 1 ? steps : K - 1;
-            }
-        }
-        if (live && A.group != nullptr) A.group[q] = A.p2g[g2];
-    }
+#define PREDICT_COUNT P.row_end
+#define PREDICT_FIRST (size_t)blockIdx.x * kBlock + threadIdx.x
+#define PREDICT_STRIDE (size_t)gridDim.x * kBlock
+#define PREDICT_ROW(item) item
+#define PREDICT_LOGP(x) x
+#include "kernels_predict_body.h"
+#undef PREDICT_COUNT
+#undef PREDICT_FIRST
+#undef PREDICT_STRIDE
+#undef PREDICT_ROW
+#undef PREDICT_LOGP
 }
 
 }  // namespace dist

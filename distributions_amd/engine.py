@@ -364,6 +364,74 @@ def sweep_sequential_many(engines, row_begin, row_end, rng_states):
                                        row_end, rng_states)
 
 
+PREDICT_MANY_DRAW_ALL = _core.PREDICT_MANY_DRAW_ALL
+
+
+def _cores(engines):
+    return [None if g is None else g.core for g in engines]
+
+
+def predict_many(engines, values, mode="sample", seed=0, member_seed=None,
+                 draw_base=0, members=False, flags=0):
+    """Rows that are NOT in the table, against M engines at once: the
+    predictive averaged over the members of an ensemble (the chains of
+    sweep_sequential_many, each one posterior sample), in launches that cover
+    every member.  values: one host array per feature.
+    -> (logp, members, groups, members_logp, prior_totals):
+    logp[q] = log (1/M) sum_e p(x_q | engine e), the in-order log_sum_exp
+    (random.cc:78-92) over the engines of `Gibbs.predict`'s logp -- under
+    LowEntropy each normalised by its own prior_total first -- minus
+    fast_log(M); members[q] is the engine drawn from those M values with
+    engine step draw_base + q + 1 of `member_seed` (None: seed + 1), or for
+    mode "map" the first engine of maximal value; groups[q] is the group
+    engines[members[q]].predict(values, mode, seed, draw_base) gives row q,
+    as that engine's global id; mode None leaves both out.  members_logp
+    (members=True) is the [M, n] array the fold ran over, prior_totals the
+    engines' prior totals.  The engines share one feature list and one
+    clustering model; nothing in them changes."""
+    if member_seed is None:
+        member_seed = seed + 1
+    return _core.predict_many(_cores(engines), list(values),
+                              Gibbs._PREDICT_MODES[mode],
+                              _core.rng_seed(seed),
+                              _core.rng_seed(member_seed), draw_base, members,
+                              flags)
+
+
+def predict_many_torch(engines, values, mode="sample", seed=0,
+                       member_seed=None, draw_base=0, members=False, flags=0):
+    """predict_many for device tensors (one 4-byte-per-row CUDA tensor per
+    feature): the results but prior_totals (numpy) are tensors on the same
+    device and nothing is staged through the host."""
+    import torch
+    if member_seed is None:
+        member_seed = seed + 1
+    values = [v.contiguous() for v in values]
+    n = int(values[0].numel())
+    m = Gibbs._PREDICT_MODES[mode]
+    dev = values[0].device
+    logp = torch.empty(n, dtype=torch.float32, device=dev)
+    chosen = groups = planes = None
+    if m is not None:
+        chosen = torch.empty(n, dtype=torch.int32, device=dev)
+        groups = torch.empty(n, dtype=torch.int32, device=dev)
+    if members:
+        planes = torch.empty((len(engines), n), dtype=torch.float32,
+                             device=dev)
+    # (the library works on its own stream: what filled the tensors on
+    # torch's must be done)
+    torch.cuda.current_stream(dev).synchronize()
+    totals = _core.predict_many_dev(
+        _cores(engines), [int(v.data_ptr()) for v in values], n,
+        int(logp.data_ptr()),
+        int(chosen.data_ptr()) if chosen is not None else 0,
+        int(groups.data_ptr()) if groups is not None else 0,
+        0 if m is None else m, _core.rng_seed(seed),
+        _core.rng_seed(member_seed), draw_base,
+        int(planes.data_ptr()) if planes is not None else 0, n, True, flags)
+    return logp, chosen, groups, planes, totals
+
+
 class ShardedGibbs(object):
     """Row-sharded Gibbs over the ranks of a torch.distributed process group.
 

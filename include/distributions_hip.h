@@ -606,6 +606,67 @@ int dist_gibbs_predict(dist_gibbs_t * g, size_t n_rows,
                        const uint32_t * const * values, float * logp_out,
                        uint32_t * group_out, int mode, uint32_t seed_state,
                        uint64_t draw_base, float * prior_total_out);
+/* Held-out rows against M engines at once: the predictive averaged over the
+ * members of an ensemble, e.g. the chains dist_gibbs_sweep_sequential_many
+ * advances, each one posterior sample of the partition and, after
+ * dist_gibbs_sample_hypers, of the hyper-parameters.  An extension: the
+ * reference has no such member, only the folds reused here.  For query row q
+ * and engine e in [0, m):
+ *   w[e][q] = logp[q] of dist_gibbs_predict on engine e, bit for bit; under
+ *     LowEntropy minus that engine's prior_total, one float subtraction (under
+ *     PitmanYor nothing is subtracted);
+ *   logp[q] = log_sum_exp(w[0..m)[q]) - fast_log((float)m): log (1/m) sum_e
+ *     p(x_q | state_e), with log_sum_exp as random.cc:78-92 has it -- the
+ *     maximum, the in-order float sum of fast_exp(w - max), fast_log(total) +
+ *     max.  For m == 1 these are dist_gibbs_predict's bits (minus prior_total
+ *     under LowEntropy).  A member value of -inf or NaN gives what that fold
+ *     gives;
+ *   member[q]: mode 0 draws the engine by sample_from_scores_overwrite
+ *     (random.hpp:361-366) over w[.][q] with engine step draw_base + q + 1 of
+ *     member_seed_state; mode 1 takes the first index that attains the
+ *     maximum;
+ *   group[q]: the group dist_gibbs_predict gives row q on engine member[q]
+ *     with the same mode, seed_state and draw_base (mode 0: engine step
+ *     draw_base + q + 1 of seed_state), as that engine's GLOBAL id.
+ *   members_logp: the planes w, plane e at members_logp + e * members_ld
+ *     (members_ld >= n_rows); prior_totals_out[e]: engine e's prior_total.
+ * values: F columns of n_rows words, every feature observed.  Every output
+ * may be NULL.  The engines are distinct and share one feature list (kinds
+ * and dim) and one clustering model; hyper-parameters, group counts, rows
+ * and id maps may all differ.  A pure reader of every engine under the rules
+ * of dist_gibbs_predict: a run a sweep left open stays resumable, an open
+ * batch or stale cells on any engine are refused, a value outside its domain
+ * fails the call naming the first such row and its feature, a
+ * DirichletProcessDiscrete value outside the table scores as OTHER.  m == 0
+ * or n_rows == 0 does nothing.  Scratch: m x chunk words per plane, chunk the
+ * most rows that keep a plane under 1 GiB and at most the first engine's
+ * "debug.predict_chunk"; results do not depend on it.  One host wait per
+ * call.
+ * flags: DIST_PREDICT_MANY_DRAW_ALL draws the group in EVERY member and
+ * selects afterwards, instead of drawing only in the chosen one (same bits;
+ * the A/B partner of the default).
+ * _dev: device pointers throughout (engines and values_dev are host arrays),
+ * prior_totals_out a host array of m floats.  The host form stages, calls
+ * and downloads. */
+#define DIST_PREDICT_MANY_DRAW_ALL 1u
+int dist_gibbs_predict_many_dev(dist_gibbs_t * const * engines, size_t m,
+                                size_t n_rows,
+                                const uint32_t * const * values_dev,
+                                float * logp_dev, uint32_t * member_dev,
+                                uint32_t * group_dev, int mode,
+                                uint32_t seed_state,
+                                uint32_t member_seed_state,
+                                uint64_t draw_base, float * members_logp_dev,
+                                size_t members_ld, float * prior_totals_out,
+                                unsigned flags);
+int dist_gibbs_predict_many(dist_gibbs_t * const * engines, size_t m,
+                            size_t n_rows, const uint32_t * const * values,
+                            float * logp_out, uint32_t * member_out,
+                            uint32_t * group_out, int mode,
+                            uint32_t seed_state, uint32_t member_seed_state,
+                            uint64_t draw_base, float * members_logp_out,
+                            size_t members_ld, float * prior_totals_out,
+                            unsigned flags);
 
 /* Held-out rows: one feature's predictive given the others.  For query row q,
  * a target feature t, candidate words cand[0..C) for t and a mask observed[q]
