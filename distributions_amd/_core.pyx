@@ -255,6 +255,16 @@ cdef extern from "distributions_hip.h" nogil:
                                    const uint32_t *, int, const uint32_t *,
                                    size_t, float *, float *, uint32_t *, int,
                                    uint32_t, uint64_t, unsigned)
+    int dist_gibbs_predict_feature_many_dev(
+        dist_gibbs_t * const *, size_t, size_t, const uint32_t * const *,
+        const uint32_t *, int, const uint32_t *, size_t, float *, float *,
+        uint32_t *, uint32_t *, int, uint32_t, uint32_t, uint64_t, float *,
+        size_t, float *, size_t, float *, unsigned) nogil
+    int dist_gibbs_predict_feature_many(
+        dist_gibbs_t * const *, size_t, size_t, const uint32_t * const *,
+        const uint32_t *, int, const uint32_t *, size_t, float *, float *,
+        uint32_t *, uint32_t *, int, uint32_t, uint32_t, uint64_t, float *,
+        size_t, float *, size_t, float *, unsigned) nogil
     int dist_gibbs_sample_rows_dev(dist_gibbs_t *, size_t,
                                    const uint32_t * const *,
                                    const uint32_t *, uint32_t * const *,
@@ -2049,3 +2059,160 @@ def predict_many(engines, values, mode, uint32_t seed_state,
     return (logp, None if mode is None else member,
             None if mode is None else group, planes if members else None,
             totals)
+
+
+def predict_feature_many_dev(engines, value_ptrs, size_t n_rows,
+                             size_t observed_ptr, int target, candidates,
+                             size_t joint_ptr, size_t base_ptr,
+                             size_t choice_ptr, size_t member_ptr, int mode,
+                             uint32_t seed_state, uint32_t member_seed_state,
+                             draw_base=0, size_t members_joint_ptr=0,
+                             size_t members_joint_ld=0,
+                             size_t members_base_ptr=0,
+                             size_t members_base_ld=0,
+                             bint prior_totals=True, unsigned flags=0):
+    """One feature's predictive averaged over M engines
+    (dist_gibbs_predict_feature_many_dev): engines = GibbsEngine objects,
+    value_ptrs device addresses of one column of n_rows words per feature (0
+    for the target's is fine), observed_ptr the device address of the rows'
+    masks or 0, candidates a host list or None (the whole domain), the other
+    pointers device addresses or 0.
+    -> the engines' prior totals (numpy float32), or None"""
+    cdef size_t m = len(engines)
+    if m == 0 or engines[0] is None:
+        raise RuntimeError("predict_feature_many: no engine" if m == 0
+                           else "null engine")
+    cdef GibbsEngine first = engines[0]
+    cdef size_t nf = len(value_ptrs)
+    if nf != len(first.shareds):
+        raise RuntimeError("one value column per feature")
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] cand = np.ascontiguousarray(
+        first.feature_candidates(target, candidates), dtype=np.uint32)
+    cdef size_t n_cand = cand.shape[0]
+    cdef const uint32_t * cand_p = (
+        NULL if candidates is None else <const uint32_t *> cand.data)
+    cdef const uint32_t ** cols = <const uint32_t **> malloc(
+        sizeof(void *) * (nf + 1))
+    cdef size_t i
+    cdef size_t addr
+    for i in range(nf):
+        addr = value_ptrs[i]
+        cols[i] = <const uint32_t *> addr
+    cdef cnp.ndarray[cnp.float32_t, ndim=1] totals = np.zeros(m, np.float32)
+    cdef float * tp = <float *> totals.data if prior_totals else NULL
+    cdef uint64_t db = <uint64_t> draw_base
+    cdef dist_gibbs_t ** ptrs
+    cdef int rc
+    try:
+        ptrs = _engine_ptrs(engines)
+    except Exception:
+        free(cols)
+        raise
+    with nogil:
+        rc = dist_gibbs_predict_feature_many_dev(
+            <dist_gibbs_t * const *> ptrs, m, n_rows, cols,
+            <const uint32_t *> observed_ptr, target, cand_p, n_cand,
+            <float *> joint_ptr, <float *> base_ptr, <uint32_t *> choice_ptr,
+            <uint32_t *> member_ptr, mode, seed_state, member_seed_state, db,
+            <float *> members_joint_ptr, members_joint_ld,
+            <float *> members_base_ptr, members_base_ld, tp, flags)
+    free(ptrs)
+    free(cols)
+    check(rc)
+    return totals.copy() if prior_totals else None
+
+
+def predict_feature_many(engines, values, int target, candidates, observed,
+                         mode, uint32_t seed_state,
+                         uint32_t member_seed_state, draw_base=0,
+                         bint members=False, unsigned flags=0):
+    """One feature's predictive averaged over M engines, from host arrays
+    (dist_gibbs_predict_feature_many): values is one array per feature (None
+    for the target's is fine), candidates a list or None (the whole domain),
+    observed one uint32 mask per row or None; mode 0 draws, 1 takes the first
+    maximum, None leaves choice and member out.
+    -> (joint [n, C], base [n], choice or None, member or None,
+    members_joint [M, n, C] or None, members_base [M, n] or None,
+    prior_totals [M])"""
+    cdef size_t m = len(engines)
+    if m == 0 or engines[0] is None:
+        raise RuntimeError("predict_feature_many: no engine" if m == 0
+                           else "null engine")
+    cdef GibbsEngine first = engines[0]
+    cdef int n = len(first.shareds)
+    if len(values) != n:
+        raise RuntimeError("one value column per feature")
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] cand = np.ascontiguousarray(
+        first.feature_candidates(target, candidates), dtype=np.uint32)
+    cdef size_t n_cand = cand.shape[0]
+    cdef const uint32_t * cand_p = (
+        NULL if candidates is None else <const uint32_t *> cand.data)
+    cdef const uint32_t ** cols = <const uint32_t **> malloc(
+        sizeof(void *) * (n + 1))
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] w
+    cdef SharedParams s
+    words = []
+    cdef int i
+    cdef Py_ssize_t rows = -1
+    for i in range(n):
+        if values[i] is None and i == target:
+            cols[i] = NULL
+            continue
+        s = first.shareds[i]
+        w = value_words(s.c.kind, values[i])
+        if rows >= 0 and w.shape[0] != rows:
+            free(cols)
+            raise RuntimeError("feature columns differ in length")
+        rows = w.shape[0]
+        words.append(w)
+        cols[i] = <const uint32_t *> w.data
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] mask
+    cdef const uint32_t * mask_p = NULL
+    if observed is not None:
+        mask = np.ascontiguousarray(observed, dtype=np.uint32)
+        if rows >= 0 and mask.shape[0] != rows:
+            free(cols)
+            raise RuntimeError("one mask per row")
+        rows = mask.shape[0]
+        mask_p = <const uint32_t *> mask.data
+    if rows < 0:
+        free(cols)
+        raise RuntimeError("predict_feature_many: no column tells the "
+                           "number of rows")
+    cdef size_t n_rows = rows
+    cdef cnp.ndarray[cnp.float32_t, ndim=2] joint = np.zeros(
+        (rows, n_cand), np.float32)
+    cdef cnp.ndarray[cnp.float32_t, ndim=1] base = np.zeros(rows, np.float32)
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] choice = np.zeros(rows, np.uint32)
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] member = np.zeros(rows, np.uint32)
+    cdef cnp.ndarray[cnp.float32_t, ndim=3] pj = np.zeros(
+        (m if members else 1, rows if members else 1,
+         n_cand if members else 1), np.float32)
+    cdef cnp.ndarray[cnp.float32_t, ndim=2] pb = np.zeros(
+        (m if members else 1, rows if members else 1), np.float32)
+    cdef cnp.ndarray[cnp.float32_t, ndim=1] totals = np.zeros(m, np.float32)
+    cdef uint32_t * cp = NULL if mode is None else <uint32_t *> choice.data
+    cdef uint32_t * mp = NULL if mode is None else <uint32_t *> member.data
+    cdef float * pjp = <float *> pj.data if members else NULL
+    cdef float * pbp = <float *> pb.data if members else NULL
+    cdef int md = 0 if mode is None else mode
+    cdef uint64_t db = <uint64_t> draw_base
+    cdef dist_gibbs_t ** ptrs
+    cdef int rc
+    try:
+        ptrs = _engine_ptrs(engines)
+    except Exception:
+        free(cols)
+        raise
+    with nogil:
+        rc = dist_gibbs_predict_feature_many(
+            <dist_gibbs_t * const *> ptrs, m, n_rows, cols, mask_p, target,
+            cand_p, n_cand, <float *> joint.data, <float *> base.data, cp,
+            mp, md, seed_state, member_seed_state, db, pjp, n_rows * n_cand,
+            pbp, n_rows, <float *> totals.data, flags)
+    free(ptrs)
+    free(cols)
+    check(rc)
+    return (joint, base, None if mode is None else choice,
+            None if mode is None else member, pj if members else None,
+            pb if members else None, totals)

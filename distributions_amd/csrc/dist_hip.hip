@@ -5196,6 +5196,76 @@ struct Gibbs {
                          + std::to_string(bad & 0xFF));
     }
 
+    // One feature's predictive averaged over M engines (kernels_feature.h,
+    // predict_feature_many below): the first engine holds the call's buffers
+    DeviceBuf<FeatureMember> fmany_args;
+    DeviceBuf<float> fmany_wj;      // [M][chunk * C] unless the caller's
+    DeviceBuf<float> fmany_wb;      // [M][chunk] unless the caller's
+    DeviceBuf<float> fmany_joint;   // [chunk][C]: choice without joint
+    // the candidate words of `target` as the kernels take them, validated
+    // (predict_feature's rules)
+    std::vector<uint32_t> feature_cand_words(int target,
+                                             const uint32_t * candidates,
+                                             size_t n_candidates,
+                                             const std::string & who) {
+        const dist_shared_t & tsh = feats[target]->sh;
+        std::vector<uint32_t> cand;
+        if (candidates == nullptr) {
+            DIST_REQUIRE(is_cat(tsh.kind) || tsh.kind == DIST_BB,
+                         who + ": this target needs a candidate list");
+            const uint32_t dim = tsh.kind == DIST_BB ? 2u : (uint32_t)tsh.dim;
+            for (uint32_t v = 0; v < dim; ++v) cand.push_back(v);
+            if (tsh.kind == DIST_DPD) cand.push_back(DIST_DPD_OTHER);
+            return cand;
+        }
+        DIST_REQUIRE(n_candidates > 0 && n_candidates < ((size_t)1 << 24),
+                     who + ": bad candidate count");
+        cand.assign(candidates, candidates + n_candidates);
+        for (size_t c = 0; c < cand.size(); ++c) {
+            const bool bad_c =
+                (tsh.kind == DIST_DD && cand[c] >= (uint32_t)tsh.dim)
+                || (tsh.kind == DIST_BB && cand[c] > 1u);
+            DIST_REQUIRE(!bad_c, who + ": candidate " + std::to_string(c)
+                                     + " is outside the target's domain");
+            // dpd.hpp:534-542: a value the table does not hold is OTHER
+            if (tsh.kind == DIST_DPD && cand[c] >= (uint32_t)tsh.dim)
+                cand[c] = DIST_DPD_OTHER;
+        }
+        return cand;
+    }
+    // the launch geometry of the staged form, the same for every member:
+    // launch_feature_staged's, the tile taken from the call's largest K
+    struct FeatureGeometry {
+        int items, rows, tile;
+        size_t lds, blocks;
+    };
+    static FeatureGeometry feature_many_geometry(size_t n_rows, int C,
+                                                 size_t k_max,
+                                                 int terms_after) {
+        const size_t S = (size_t)C + 1;
+        size_t items = kBlock;
+        if ((items - 1) / S + 2 > (size_t)kFeatureRowsMax)
+            items = (size_t)(kFeatureRowsMax - 2) * S + 1;
+        int rows = (int)((items - 1) / S + 2);
+        rows = (int)std::min<size_t>((size_t)rows, n_rows + 1);
+        const size_t per_k = predict_feature_lds(terms_after, 0, rows);
+        const int tile = (int)std::min<size_t>(k_max,
+                                               kFeatureLdsBudget / per_k - 1);
+        FeatureGeometry g;
+        g.items = (int)items;
+        g.rows = rows;
+        g.tile = std::max(tile, 1);
+        g.lds = predict_feature_lds(terms_after, g.tile, rows);
+        g.blocks = (n_rows * S + items - 1) / items;
+        return g;
+    }
+    template <int TK>
+    static void launch_feature_many(const FeatureMember * args, unsigned m,
+                                    const FeatureGeometry & g) {
+        launch_lds<&k_predict_feature_many<TK>>(
+            dim3((unsigned)g.blocks, m), dim3(kBlock), g.lds, args);
+    }
+
     // Whole rows and missing cells drawn from the mixture (kernels_sample.h)
     DeviceBuf<float> sample_lik;      // [K + 1]: the nothing-observed instance
     DeviceBuf<float> sample_w[kMaxF]; // DPD betas
@@ -5564,6 +5634,18 @@ struct Gibbs {
                              uint64_t draw_base, float * members_logp_dev,
                              size_t members_ld, float * prior_totals_out,
                              unsigned flags);
+    // one feature's predictive averaged over M engines (kernels_feature.h;
+    // defined behind GibbsRef as well)
+    static void predict_feature_many(
+        dist_gibbs_t * const * engines, size_t m, size_t n,
+        const uint32_t * const * values_dev, const uint32_t * observed_dev,
+        int target, const uint32_t * candidates, size_t n_candidates,
+        float * joint_dev, float * base_dev, uint32_t * choice_dev,
+        uint32_t * member_dev, int mode, uint32_t seed_state,
+        uint32_t member_seed_state, uint64_t draw_base,
+        float * members_joint_dev, size_t members_joint_ld,
+        float * members_base_dev, size_t members_base_ld,
+        float * prior_totals_out, unsigned flags);
 };
 
 }  // namespace dist
@@ -5850,6 +5932,232 @@ void dist::Gibbs::predict_many(dist_gibbs_t * const * engines, size_t m,
         memcpy(prior_totals_out, pinned + 64, m * sizeof(float));
     DIST_REQUIRE(bad == ~0ull,
                  "predict_many: value outside its feature's domain at row "
+                     + std::to_string(bad >> 8) + ", feature "
+                     + std::to_string(bad & 0xFF));
+}
+
+void dist::Gibbs::predict_feature_many(
+        dist_gibbs_t * const * engines, size_t m, size_t n,
+        const uint32_t * const * values_dev, const uint32_t * observed_dev,
+        int target, const uint32_t * candidates, size_t n_candidates,
+        float * joint_dev, float * base_dev, uint32_t * choice_dev,
+        uint32_t * member_dev, int mode, uint32_t seed_state,
+        uint32_t member_seed_state, uint64_t draw_base,
+        float * members_joint_dev, size_t members_joint_ld,
+        float * members_base_dev, size_t members_base_ld,
+        float * prior_totals_out, unsigned flags) {
+    const std::string who = "predict_feature_many";
+    DIST_REQUIRE(mode == 0 || mode == 1,
+                 who + ": mode is 0 (draw) or 1 (first maximum)");
+    DIST_REQUIRE(flags == 0, who + ": unknown flag");
+    DIST_REQUIRE(m == 0 || engines, "null argument");
+    if (!m) return;
+    DIST_REQUIRE(m <= 65535, who + ": at most 65535 engines");
+    std::vector<Gibbs *> e(m);
+    for (size_t i = 0; i < m; ++i) {
+        DIST_REQUIRE(engines[i], "null engine");
+        e[i] = engines[i]->impl.read();   // (settles, stays resumable)
+        for (size_t j = 0; j < i; ++j)
+            DIST_REQUIRE(e[j] != e[i], "the same engine twice");
+        DIST_REQUIRE(e[i]->F() == e[0]->F(), "engines of one feature list");
+        for (int f = 0; f < e[0]->F(); ++f)
+            DIST_REQUIRE(e[i]->feats[f]->sh.kind == e[0]->feats[f]->sh.kind
+                             && e[i]->feats[f]->sh.dim
+                                    == e[0]->feats[f]->sh.dim,
+                         "engines of one feature list");
+        DIST_REQUIRE(e[i]->cluster == e[0]->cluster,
+                     "engines of one clustering model");
+        // the caches it reads are the frozen state's only between batches
+        DIST_REQUIRE(!e[i]->batch_open, "batch open");
+        e[i]->ex.require_whole(who.c_str());
+    }
+    Gibbs & first = *e[0];
+    const int F = first.F();
+    DIST_REQUIRE(target >= 0 && target < F,
+                 who + ": no such target feature");
+    // the candidate words, validated once, before any launch, against the
+    // shared feature list
+    const std::vector<uint32_t> cand =
+        first.feature_cand_words(target, candidates, n_candidates, who);
+    if (!n) return;
+    DIST_REQUIRE(values_dev != nullptr, "null argument");
+    for (int f = 0; f < F; ++f)
+        DIST_REQUIRE(values_dev[f] != nullptr || f == target,
+                     "null value column");
+    const size_t C = cand.size();
+    DIST_REQUIRE(!members_joint_dev || members_joint_ld / C >= n,
+                 who + ": members_joint_ld is less than rows x candidates");
+    DIST_REQUIRE(!members_base_dev || members_base_ld >= n,
+                 who + ": members_base_ld is less than the row count");
+    const bool le = first.cluster == 1;
+    const bool want_totals = le || prior_totals_out != nullptr;
+    const bool fold_joint = joint_dev != nullptr || choice_dev != nullptr;
+    const bool fold_base = base_dev != nullptr || member_dev != nullptr;
+    const bool scratch = choice_dev != nullptr && joint_dev == nullptr;
+    // candidates the kernel scores: none when only the `base` chain is asked
+    const size_t Ck = fold_joint || members_joint_dev != nullptr ? C : 0;
+    const bool want_wb = fold_base || members_base_dev != nullptr;
+    size_t step = std::min(n, (size_t)first.opt.predict_chunk);
+    // (m x chunk x C words of scratch at the most)
+    const size_t per_row = m * std::max<size_t>(Ck, 1);
+    step = std::min(step, std::max<size_t>(1, kManyScratchWords / per_row));
+    // (the 1-D grid: at least one item per workgroup)
+    step = std::min(step, std::max<size_t>(1, (size_t)INT_MAX / (C + 1)));
+
+    first.many_args.reserve(grow_capacity(m), 0);
+    first.fmany_args.reserve(grow_capacity(m), 0);
+    if (Ck && !members_joint_dev) first.fmany_wj.reserve(m * step * C, 0);
+    if (want_wb && !members_base_dev) first.fmany_wb.reserve(m * step, 0);
+    if (scratch) first.fmany_joint.reserve(step * C, 0);
+    if (want_totals) first.many_totals.reserve(grow_capacity(m), 0);
+    first.feature_cand.upload(cand.data(), C);
+    first.predict_bad.reserve(1, 0);
+    HIP_CHECK(hipMemsetAsync(first.predict_bad.p, 0xFF,
+                             sizeof(unsigned long long), stream()));
+    first.ensure_pow_tables(step);
+    int terms_after = 0;
+    for (int f = target + 1; f < F; ++f)
+        terms_after += is_cat(first.feats[f]->sh.kind) ? 2 : 1;
+    std::vector<FeatureMember> args(m);
+    memset(args.data(), 0, m * sizeof(FeatureMember));
+    // (k_predict_prior_many and k_predict_prior_totals take PredictMembers)
+    std::vector<PredictMember> prior_args(m);
+    memset(prior_args.data(), 0, m * sizeof(PredictMember));
+    size_t k_max = 0;
+    for (size_t i = 0; i < m; ++i) {
+        Gibbs & g = *e[i];
+        g.upload_maps();
+        FeatureMember & fm = args[i];
+        fm.P = g.params(0, 0, seed_state, draw_base);
+        g.prepare_base(fm.P);
+        const size_t Kn = (size_t)g.K();
+        k_max = std::max(k_max, Kn);
+        g.predict_prior.reserve(grow_capacity(Kn), 0);
+        fm.prior = g.predict_prior.p;
+        fm.total = want_totals ? first.many_totals.p + i : nullptr;
+        fm.sub = le ? fm.total : nullptr;
+        PredictMember & pm = prior_args[i];
+        pm.P = fm.P;
+        pm.prior = fm.prior;
+        pm.total = fm.total;
+        pm.sub = fm.sub;
+    }
+    const dist_shared_t & tsh = first.feats[target]->sh;
+    for (size_t c0 = 0; c0 < n; c0 += step) {
+        const size_t c1 = std::min(n, c0 + step);
+        const size_t rows = c1 - c0;
+        float * const wj = !Ck ? nullptr
+                           : members_joint_dev ? members_joint_dev + c0 * C
+                                               : first.fmany_wj.p;
+        const size_t ldj = members_joint_dev ? members_joint_ld : step * C;
+        float * const wb = !want_wb ? nullptr
+                           : members_base_dev ? members_base_dev + c0
+                                              : first.fmany_wb.p;
+        const size_t ldb = members_base_dev ? members_base_ld : step;
+        const FeatureGeometry geo =
+            feature_many_geometry(rows, (int)Ck, k_max, terms_after);
+        for (size_t i = 0; i < m; ++i) {
+            FeatureMember & fm = args[i];
+            for (int f = 0; f < F; ++f)
+                fm.P.values[f] = values_dev[f] ? values_dev[f] + c0 : nullptr;
+            fm.P.row_begin = 0;
+            fm.P.row_end = rows;
+            fm.P.seed_batch = lcg_jump(seed_state, draw_base + c0 + 1ull);
+            fm.A.prior = fm.prior;
+            fm.A.observed = observed_dev ? observed_dev + c0 : nullptr;
+            fm.A.cand = first.feature_cand.p;
+            fm.A.target = target;
+            fm.A.C = (int)Ck;
+            fm.A.items = geo.items;
+            fm.A.rows = geo.rows;
+            fm.A.tile = geo.tile;
+            fm.A.joint = wj ? wj + i * ldj : nullptr;
+            fm.A.base = wb ? wb + i * ldb : nullptr;
+            fm.A.q0 = (unsigned long long)c0;
+            fm.A.bad = first.predict_bad.p;
+        }
+        first.fmany_args.upload(args.data(), m);
+        if (c0 == 0) {
+            first.many_args.upload(prior_args.data(), m);
+            hipLaunchKernelGGL(k_predict_prior_many,
+                               dim3(grid_for(k_max).x, (unsigned)m),
+                               dim3(kBlock), 0, stream(), first.many_args.p);
+            HIP_CHECK(hipGetLastError());
+            if (want_totals) {
+                hipLaunchKernelGGL(k_predict_prior_totals,
+                                   grid_for(m, 64), dim3(64), 0, stream(),
+                                   first.many_args.p, (int)m);
+                HIP_CHECK(hipGetLastError());
+            }
+        }
+        switch (tsh.kind) {
+        case DIST_DD:
+        case DIST_DPD:
+            launch_feature_many<DIST_DD>(first.fmany_args.p, (unsigned)m, geo);
+            break;
+        case DIST_BB:
+            launch_feature_many<DIST_BB>(first.fmany_args.p, (unsigned)m, geo);
+            break;
+        case DIST_GP:
+            launch_feature_many<DIST_GP>(first.fmany_args.p, (unsigned)m, geo);
+            break;
+        case DIST_BNB:
+            launch_feature_many<DIST_BNB>(first.fmany_args.p, (unsigned)m,
+                                          geo);
+            break;
+        default:
+            launch_feature_many<DIST_NICH>(first.fmany_args.p, (unsigned)m,
+                                           geo);
+            break;
+        }
+        float * const joint = scratch ? first.fmany_joint.p
+                              : joint_dev ? joint_dev + c0 * C : nullptr;
+        if (fold_joint) {
+            EnsembleFold fold;
+            memset(&fold, 0, sizeof(fold));
+            fold.w = wj;
+            fold.ld = ldj;
+            fold.m = (int)m;
+            fold.items = rows * C;
+            fold.logp = joint;
+            LAUNCH(k_ensemble_fold, rows * C, fold);
+        }
+        if (fold_base) {
+            EnsembleFold fold;
+            memset(&fold, 0, sizeof(fold));
+            fold.w = wb;
+            fold.ld = ldb;
+            fold.m = (int)m;
+            fold.items = rows;
+            fold.logp = base_dev ? base_dev + c0 : nullptr;
+            fold.member = member_dev ? member_dev + c0 : nullptr;
+            fold.mode = mode;
+            fold.seed_batch =
+                lcg_jump(member_seed_state, draw_base + c0 + 1ull);
+            fold.pow_lo = first.pow_lo.p;
+            fold.pow_hi = first.pow_hi.p;
+            LAUNCH(k_ensemble_fold, rows, fold);
+        }
+        if (choice_dev != nullptr)
+            LAUNCH(k_predict_feature_choice, rows, args[0].P, joint, (int)C,
+                   mode, choice_dev + c0);
+    }
+    // the call's one wait: the word of the bad values and the prior totals
+    char * pinned = chain_pinned(64 + m * sizeof(float));
+    HIP_CHECK(hipMemcpyAsync(pinned, first.predict_bad.p,
+                             sizeof(unsigned long long),
+                             hipMemcpyDeviceToHost, stream()));
+    if (prior_totals_out)
+        HIP_CHECK(hipMemcpyAsync(pinned + 64, first.many_totals.p,
+                                 m * sizeof(float), hipMemcpyDeviceToHost,
+                                 stream()));
+    HIP_CHECK(hipStreamSynchronize(stream()));
+    unsigned long long bad = 0;
+    memcpy(&bad, pinned, sizeof(bad));
+    if (prior_totals_out)
+        memcpy(prior_totals_out, pinned + 64, m * sizeof(float));
+    DIST_REQUIRE(bad == ~0ull,
+                 who + ": value outside its feature's domain at row "
                      + std::to_string(bad >> 8) + ", feature "
                      + std::to_string(bad & 0xFF));
 }
@@ -7058,6 +7366,105 @@ int dist_gibbs_predict_feature(dist_gibbs_t * g, size_t n_rows,
         if (joint_out) joint.download(joint_out, n_rows * C);
         if (base_out) base.download(base_out, n_rows);
         if (choice_out) choice.download(choice_out, n_rows);
+    });
+}
+int dist_gibbs_predict_feature_many_dev(
+        dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+        const uint32_t * const * values_dev, const uint32_t * observed_dev,
+        int target, const uint32_t * candidates, size_t n_candidates,
+        float * joint_dev, float * base_dev, uint32_t * choice_dev,
+        uint32_t * member_dev, int mode, uint32_t seed_state,
+        uint32_t member_seed_state, uint64_t draw_base,
+        float * members_joint_dev, size_t members_joint_ld,
+        float * members_base_dev, size_t members_base_ld,
+        float * prior_totals_out, unsigned flags) {
+    return guarded([&] {
+        Gibbs::predict_feature_many(
+            engines, m, n_rows, values_dev, observed_dev, target, candidates,
+            n_candidates, joint_dev, base_dev, choice_dev, member_dev, mode,
+            seed_state, member_seed_state, draw_base, members_joint_dev,
+            members_joint_ld, members_base_dev, members_base_ld,
+            prior_totals_out, flags);
+    });
+}
+int dist_gibbs_predict_feature_many(
+        dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+        const uint32_t * const * values, const uint32_t * observed,
+        int target, const uint32_t * candidates, size_t n_candidates,
+        float * joint_out, float * base_out, uint32_t * choice_out,
+        uint32_t * member_out, int mode, uint32_t seed_state,
+        uint32_t member_seed_state, uint64_t draw_base,
+        float * members_joint_out, size_t members_joint_ld,
+        float * members_base_out, size_t members_base_ld,
+        float * prior_totals_out, unsigned flags) {
+    return guarded([&] {
+        DIST_REQUIRE(m == 0 || engines, "null argument");
+        std::vector<DeviceBuf<uint32_t>> cols;
+        std::vector<const uint32_t *> ptrs;
+        // the candidate count as the engines will see it
+        size_t C = n_candidates;
+        if (m && engines[0]) {
+            Gibbs * e = engines[0]->impl.read();
+            const int F = e->F();
+            DIST_REQUIRE(target >= 0 && target < F,
+                         "predict_feature_many: no such target feature");
+            if (candidates == nullptr) {
+                const dist_shared_t & sh = e->feats[target]->sh;
+                C = sh.kind == DIST_BB ? 2
+                    : sh.kind == DIST_DPD ? (size_t)sh.dim + 1
+                                          : (size_t)sh.dim;
+            }
+            DIST_REQUIRE(values != nullptr || n_rows == 0, "null argument");
+            cols.resize((size_t)F);
+            ptrs.resize((size_t)F);
+            for (int f = 0; f < F && n_rows; ++f) {
+                DIST_REQUIRE(values[f] != nullptr || f == target,
+                             "null value column");
+                if (values[f] == nullptr) continue;
+                cols[f].upload(values[f], n_rows);
+                ptrs[f] = cols[f].p;
+            }
+        }
+        C = std::max<size_t>(C, 1);
+        DIST_REQUIRE(!members_joint_out || members_joint_ld / C >= n_rows,
+                     "predict_feature_many: members_joint_ld is less than "
+                     "rows x candidates");
+        DIST_REQUIRE(!members_base_out || members_base_ld >= n_rows,
+                     "predict_feature_many: members_base_ld is less than the "
+                     "row count");
+        const size_t cells = std::max<size_t>(n_rows, 1);
+        const size_t mm = std::max<size_t>(m, 1);
+        DeviceBuf<uint32_t> mask, choice, member;
+        DeviceBuf<float> joint, base, pj, pb;
+        if (observed && n_rows) mask.upload(observed, n_rows);
+        if (joint_out) joint.reserve(cells * C, 0);
+        if (base_out) base.reserve(cells, 0);
+        if (choice_out) choice.reserve(cells, 0);
+        if (member_out) member.reserve(cells, 0);
+        if (members_joint_out) pj.reserve(mm * cells * C, 0);
+        if (members_base_out) pb.reserve(mm * cells, 0);
+        Gibbs::predict_feature_many(
+            engines, m, n_rows, ptrs.data(),
+            observed && n_rows ? mask.p : nullptr, target, candidates,
+            n_candidates, joint.p, base.p, choice.p, member.p, mode,
+            seed_state, member_seed_state, draw_base, pj.p, n_rows * C, pb.p,
+            n_rows, prior_totals_out, flags);
+        if (!m || !n_rows) return;
+        if (joint_out) joint.download(joint_out, n_rows * C);
+        if (base_out) base.download(base_out, n_rows);
+        if (choice_out) choice.download(choice_out, n_rows);
+        if (member_out) member.download(member_out, n_rows);
+        if (members_joint_out)
+            HIP_CHECK(hipMemcpy2DAsync(
+                members_joint_out, members_joint_ld * sizeof(float), pj.p,
+                n_rows * C * sizeof(float), n_rows * C * sizeof(float), m,
+                hipMemcpyDeviceToHost, stream()));
+        if (members_base_out)
+            HIP_CHECK(hipMemcpy2DAsync(
+                members_base_out, members_base_ld * sizeof(float), pb.p,
+                n_rows * sizeof(float), n_rows * sizeof(float), m,
+                hipMemcpyDeviceToHost, stream()));
+        if (members_joint_out || members_base_out) dist::sync();
     });
 }
 int dist_gibbs_sample_rows_dev(dist_gibbs_t * g, size_t n_rows,

@@ -432,6 +432,97 @@ def predict_many_torch(engines, values, mode="sample", seed=0,
     return logp, chosen, groups, planes, totals
 
 
+def predict_feature_many(engines, values, target, candidates=None,
+                         observed=None, mode="map", seed=0, member_seed=None,
+                         draw_base=0, members=False):
+    """Given some cells of rows that are NOT in the table, the cell that is
+    missing, against M engines at once: feature `target`'s predictive given
+    the others, averaged over the members of an ensemble (the chains of
+    sweep_sequential_many, each one posterior sample).  values, candidates
+    and observed are `Gibbs.predict_feature`'s.
+    -> (joint [n, C], base [n], choice, member, members_joint, members_base,
+    prior_totals):
+    joint[q, c] = log (1/M) sum_e p(x_t = candidates[c], observed cells |
+    engine e) and base[q] = log (1/M) sum_e p(observed cells | engine e): the
+    in-order log_sum_exp (random.cc:78-92) over the engines of
+    `Gibbs.predict_feature`'s joint and base -- under LowEntropy each minus
+    that engine's prior_total first -- minus fast_log(M).
+    joint - base[:, None] is the ensemble's log conditional of the target.  It
+    is a RATIO OF AVERAGES, sum_e p(x_t, x_obs | e) / sum_e p(x_obs | e): the
+    members' conditionals weighted by how well each member explains the
+    observed cells.  It is NOT the mean of the members' joint - base, which a
+    loop over predict_feature would give and which weights every member
+    alike; under LowEntropy the members' unnormalised driver mass does not
+    cancel in it either, each member having its own.
+    choice[q] indexes the candidates: mode "sample" draws it from the folded
+    joint[q] with engine step draw_base + q + 1 of `seed`, "map" takes the
+    first maximum.  member[q] is the engine drawn from the members' base
+    values, the posterior over the members given the observed cells, with
+    engine step draw_base + q + 1 of `member_seed` (None: seed + 1), or for
+    "map" the first engine of maximal value; `member`, then sample_rows on
+    that engine, draws the missing cells from the ensemble.  mode None leaves
+    both out.  members_joint [M, n, C] and members_base [M, n]
+    (members=True) are the planes the folds ran over, prior_totals the
+    engines' prior totals.  The engines share one feature list and one
+    clustering model; nothing in them changes."""
+    if member_seed is None:
+        member_seed = seed + 1
+    return _core.predict_feature_many(
+        _cores(engines), list(values), target, candidates, observed,
+        Gibbs._PREDICT_MODES[mode], _core.rng_seed(seed),
+        _core.rng_seed(member_seed), draw_base, members)
+
+
+def predict_feature_many_torch(engines, values, target, candidates=None,
+                               observed=None, mode="map", seed=0,
+                               member_seed=None, draw_base=0, members=False):
+    """predict_feature_many for device tensors (one 4-byte-per-row CUDA tensor
+    per feature, the target's may be None; observed a CUDA int32 tensor or
+    None; candidates stay a host list): the results but prior_totals (numpy)
+    are tensors on the same device and nothing is staged through the host.
+    joint - base[:, None] is the ensemble's conditional, a ratio of averages
+    and not the mean of the members' conditionals (see predict_feature_many).
+    -> (joint, base, choice, member, members_joint, members_base,
+    prior_totals)"""
+    import torch
+    if member_seed is None:
+        member_seed = seed + 1
+    values = [None if v is None else v.contiguous() for v in values]
+    given = [v for v in values if v is not None]
+    if observed is not None:
+        observed = observed.contiguous()
+    ref = given[0] if given else observed
+    n = int(ref.numel())
+    dev = ref.device
+    m = Gibbs._PREDICT_MODES[mode]
+    C = len(engines[0].core.feature_candidates(target, candidates))
+    joint = torch.empty((n, C), dtype=torch.float32, device=dev)
+    base = torch.empty(n, dtype=torch.float32, device=dev)
+    choice = chosen = pj = pb = None
+    if m is not None:
+        choice = torch.empty(n, dtype=torch.int32, device=dev)
+        chosen = torch.empty(n, dtype=torch.int32, device=dev)
+    if members:
+        pj = torch.empty((len(engines), n, C), dtype=torch.float32,
+                         device=dev)
+        pb = torch.empty((len(engines), n), dtype=torch.float32, device=dev)
+    # (the library works on its own stream: what filled the tensors on
+    # torch's must be done)
+    torch.cuda.current_stream(dev).synchronize()
+    totals = _core.predict_feature_many_dev(
+        _cores(engines),
+        [0 if v is None else int(v.data_ptr()) for v in values], n,
+        0 if observed is None else int(observed.data_ptr()), target,
+        candidates, int(joint.data_ptr()), int(base.data_ptr()),
+        int(choice.data_ptr()) if choice is not None else 0,
+        int(chosen.data_ptr()) if chosen is not None else 0,
+        0 if m is None else m, _core.rng_seed(seed),
+        _core.rng_seed(member_seed), draw_base,
+        int(pj.data_ptr()) if pj is not None else 0, n * C,
+        int(pb.data_ptr()) if pb is not None else 0, n, True)
+    return joint, base, choice, chosen, pj, pb, totals
+
+
 class ShardedGibbs(object):
     """Row-sharded Gibbs over the ranks of a torch.distributed process group.
 

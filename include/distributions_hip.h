@@ -735,6 +735,86 @@ int dist_gibbs_predict_feature(dist_gibbs_t * g, size_t n_rows,
                                float * base_out, uint32_t * choice_out,
                                int mode, uint32_t seed_state,
                                uint64_t draw_base, unsigned flags);
+/* Held-out rows: one feature's predictive given the others, averaged over the
+ * members of an ensemble of M engines (dist_gibbs_predict_many's ensembles).
+ * An extension: the reference has no such member, only the folds reused here.
+ * For query row q, target t, candidate words cand[0..C), mask observed[q]
+ * (the bits of dist_gibbs_predict_feature: bit t is ignored, observed == NULL
+ * means every other feature is observed) and engine e in [0, m):
+ *   wj[e][q * C + c] = joint[q * C + c] of dist_gibbs_predict_feature on
+ *     engine e, bit for bit; under LowEntropy minus that engine's prior_total,
+ *     one float subtraction (under PitmanYor nothing is subtracted);
+ *   wb[e][q] = the same for base[q];
+ *   joint[q * C + c] = log_sum_exp(wj[0..m)[q * C + c]) - fast_log((float)m)
+ *     and base[q] = log_sum_exp(wb[0..m)[q]) - fast_log((float)m), with
+ *     log_sum_exp as random.cc:78-92 has it -- the maximum, the in-order float
+ *     sum of fast_exp(w - max), fast_log(total) + max: the logs of
+ *     (1/m) sum_e p(x_t = cand[c], x_obs | e) and (1/m) sum_e p(x_obs | e).
+ *     For m == 1 these are dist_gibbs_predict_feature's bits (minus
+ *     prior_total under LowEntropy);
+ *   the ensemble's conditional log p(x_t = cand[c] | x_obs) is joint - base,
+ *     which the caller forms: a RATIO OF AVERAGES,
+ *       sum_e p(x_t, x_obs | e) / sum_e p(x_obs | e),
+ *     the members' conditionals weighted by how well each explains the
+ *     observed cells (p(e | x_obs) is proportional to p(x_obs | e)).  It is
+ *     not the mean over e of the members' joint - base, which weights every
+ *     member alike whatever the row shows.  Under LowEntropy each member's
+ *     unnormalised driver mass is its own and no longer cancels in the ratio,
+ *     hence the subtraction above;
+ *   choice[q], an INDEX into the candidates: mode 0 draws it by
+ *     sample_from_scores_overwrite (random.hpp:361-366) over the FOLDED
+ *     joint[q][0..C) with engine step draw_base + q + 1 of seed_state; mode 1
+ *     takes the first index of maximal folded joint;
+ *   member[q]: the engine drawn from wb[.][q], the posterior over the members
+ *     given the observed cells: mode 0 by sample_from_scores_overwrite with
+ *     engine step draw_base + q + 1 of member_seed_state, mode 1 the first
+ *     maximum.  (member, then dist_gibbs_sample_rows on that engine, composes
+ *     an ensemble draw of the missing cells.)
+ *   members_joint: the planes wj, plane e at members_joint + e *
+ *     members_joint_ld (members_joint_ld >= n_rows * C); members_base: the
+ *     planes wb, plane e at members_base + e * members_base_ld
+ *     (members_base_ld >= n_rows); prior_totals_out[e]: engine e's
+ *     prior_total, a HOST array of m floats.
+ * Every output may be NULL.  When neither joint, choice nor members_joint is
+ * asked for, only the base chain runs.
+ * candidates: a HOST array in both forms, validated once, before any launch,
+ * against the shared feature list by dist_gibbs_predict_feature's rules (a
+ * DirichletDiscrete word >= dim or a BetaBernoulli word > 1 fails naming the
+ * candidate's index, a DirichletProcessDiscrete word outside the table is
+ * OTHER, NULL is the whole domain of a DD, BB or DPD target).  An observed
+ * value outside its domain fails the call naming the first such row and its
+ * feature; words in unobserved cells are never read; the target's column may
+ * be NULL.  The engines are distinct and share one feature list (kinds and
+ * dim) and one clustering model, at most 65535 of them.  A pure reader of
+ * every engine under dist_gibbs_predict_many's rules: a run a sweep left open
+ * stays resumable, an open batch or stale cells on any engine are refused.
+ * m == 0 or n_rows == 0 does nothing.  flags must be 0.  Scratch: m x chunk x
+ * C words for wj unless members_joint is given, m x chunk for wb unless
+ * members_base is, chunk x C for joint when choice is asked without it; chunk
+ * keeps m x chunk x C words under 1 GiB and is at most the first engine's
+ * "debug.predict_chunk"; results do not depend on it or on launch geometry.
+ * One host wait per call.
+ * _dev: device pointers throughout; engines, values_dev (F device pointers),
+ * candidates and prior_totals_out are host arrays.  The host form stages,
+ * calls and downloads. */
+int dist_gibbs_predict_feature_many_dev(
+    dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+    const uint32_t * const * values_dev, const uint32_t * observed_dev,
+    int target, const uint32_t * candidates, size_t n_candidates,
+    float * joint_dev, float * base_dev, uint32_t * choice_dev,
+    uint32_t * member_dev, int mode, uint32_t seed_state,
+    uint32_t member_seed_state, uint64_t draw_base, float * members_joint_dev,
+    size_t members_joint_ld, float * members_base_dev, size_t members_base_ld,
+    float * prior_totals_out, unsigned flags);
+int dist_gibbs_predict_feature_many(
+    dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+    const uint32_t * const * values, const uint32_t * observed, int target,
+    const uint32_t * candidates, size_t n_candidates, float * joint_out,
+    float * base_out, uint32_t * choice_out, uint32_t * member_out, int mode,
+    uint32_t seed_state, uint32_t member_seed_state, uint64_t draw_base,
+    float * members_joint_out, size_t members_joint_ld,
+    float * members_base_out, size_t members_base_ld,
+    float * prior_totals_out, unsigned flags);
 
 /* Held-out rows: whole rows and missing cells drawn from the mixture.  Per
  * query row q with mask observed[q] (bit f set: feature f of row q is
