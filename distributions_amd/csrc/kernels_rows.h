@@ -96,14 +96,33 @@ __device__ __forceinline__ uniform_fp as_uniform(const float * p) {
     return (uniform_fp)(unsigned long long)p;
 }
 
+// one wave-uniform word of read-only data, into a scalar register
+template <class T>
+__device__ __forceinline__ T uniform_load(const T * p) {
+    typedef const T __attribute__((address_space(4))) * uniform_p;
+    return *(uniform_p)(unsigned long long)p;
+}
+
 // sample_unif01 of batch row b (random.hpp:47-50): one engine step per row,
-// the step the sequential chain would have used for it
+// the step the sequential chain would have used for it.  In two halves for
+// the kernels that request several rows' table words before they wait for
+// any: the gathers (b = row - row_begin), then the arithmetic.
+struct RowDrawWords {
+    uint32_t lo, hi;
+};
+__device__ __forceinline__ RowDrawWords batch_row_draw_words(
+        const SweepParams & P, size_t b) {
+    return {P.pow_lo[b & 4095], P.pow_hi[b >> 12]};
+}
+__device__ __forceinline__ float batch_row_draw_unif01(const SweepParams & P,
+                                                       RowDrawWords w) {
+    uint32_t xs = lcg_mulmod(P.seed_batch, w.lo);
+    xs = lcg_mulmod(xs, w.hi);
+    return lcg_unif01(xs);
+}
 __device__ __forceinline__ float batch_row_unif01(const SweepParams & P,
                                                   size_t row) {
-    const size_t b = row - P.row_begin;
-    uint32_t xs = lcg_mulmod(P.seed_batch, P.pow_lo[b & 4095]);
-    xs = lcg_mulmod(xs, P.pow_hi[b >> 12]);
-    return lcg_unif01(xs);
+    return batch_row_draw_unif01(P, batch_row_draw_words(P, row - P.row_begin));
 }
 
 __global__ void k_pow_tables(uint32_t * pow_lo, uint32_t * pow_hi,

@@ -43,6 +43,14 @@ struct VsTile {
     uint32_t n;      // rows in the tile (<= 64 * kVsR)
     uint32_t chunk;  // the apply chunk (k_vs_apply work item) the rows lie in
 };
+// a wave's tile descriptor, by one scalar load (the tile lists are arrays of
+// these 16-byte records in buffers of their own)
+static_assert(sizeof(VsTile) == 16, "vs_load_tile reads one 16-byte record");
+__device__ __forceinline__ VsTile vs_load_tile(const VsTile * p) {
+    typedef uint32_t words __attribute__((ext_vector_type(4)));
+    const words w = uniform_load(reinterpret_cast<const words *>(p));
+    return {w.x, w.y, w.z, w.w};
+}
 // Where a tile leaves the rows its shortcut does not cover.  Either ONE list
 // for the launch (`list`, `count`: a wave-per-row launch follows), or -- when
 // `chunk_counts` is set -- a list per apply chunk, kept in the chunk's own
@@ -1103,6 +1111,8 @@ __device__ __forceinline__ void vs_sum_and_scan(
     // t never increases, so the number of chunks that END with t > 0 is the
     // chunk in which the lane crosses zero, and the last such end value is
     // the value it enters that chunk with: three operations per chunk
+    // (K comes by a scalar load -- k_vs_sample's stage 0 -- so the trip
+    // count, k0 < K and the priority switch are the scalar unit's)
     v2f t = total * (v2f){u[0], u[1]};
     float t_start[kVsR] = {t.x, t.y};
     int npos[kVsR] = {0, 0};
@@ -1224,82 +1234,116 @@ void k_vs_sample(
     const bool band = id < n_band_ids;
     const VsTile * mine = band ? T.band_tile + id : tiles + (id - n_band_ids);
     if (band ? id >= T.band_count : id - n_band_ids >= n_tiles) return;
-    const uint32_t x = __builtin_amdgcn_readfirstlane(mine->x);
-    const uint32_t pos = __builtin_amdgcn_readfirstlane(mine->pos);
-    const uint32_t n = __builtin_amdgcn_readfirstlane(mine->n);
+    // The set-up is a chain of dependent trips to memory, and all the
+    // launch's waves make it at the same moment.  So it runs in stages: a
+    // stage requests what BOTH rows of a lane need next, without a wait or a
+    // data-dependent branch inside it.  Lanes without a row, and rows the
+    // tile turns out to skip or hand over, load like the others -- the former
+    // through the tile's last row, so every address stays inside its array --
+    // and drop what they loaded.
+    // Stage 0, wave-uniform words (scalar loads; they stay in SGPRs): the
+    // tile, and -- beside stage 1's loads -- the value's words
+    const VsTile tile = vs_load_tile(mine);
+    const uint32_t x = tile.x, pos = tile.pos, n = tile.n;
+    const uint32_t my_chunk = tile.chunk;
     if (n == 0) return;
-    const bool skip_a = band;
-    const bool skip_b =
-        !band && n_band_ids != 0
-        && T.band_mode[T.band_by_chunk ? mine->chunk : x] != 0;
-    SlaveView v = P.feat[0];
-    v.kind = KIND;
-    const int K = sweep_K(P);
-    const float shift = P.scalars->shift;
-    const float M = T.M[x], mB = T.mB[x];
-    const int amax = T.argmax[x];
-    const float ea = u2f(g_tables_dev.exp_ab[0]);
-    const float eb = u2f(g_tables_dev.exp_ab[1]);
-    const float lf = KIND == DIST_GP ? fast_log_factorial(x) : 0.f;
 
     bool valid[kVsR], inA[kVsR], inB[kVsR];
-    size_t row[kVsR];
+    uint32_t at[kVsR];
     int g[kVsR], g2[kVsR];
     float l_own[kVsR], u[kVsR], total[kVsR];
     bool anyA = false, anyB = false;
     const bool shared = T.tot != nullptr;   // (only with T.own)
+    // Stage 1: the rows and their chain ids
+    uint32_t b[kVsR], chain[kVsR];
 #pragma unroll
     for (int r = 0; r < kVsR; ++r) {
         valid[r] = (uint32_t)(kVsR * lane + r) < n;
-        row[r] = 0;
-        g[r] = -1;
+        at[r] = valid[r] ? pos + kVsR * lane + r : pos + n - 1;
+        b[r] = sorted_rows[at[r]];   // (row = P.row_begin + b)
+        chain[r] = P.assign_pos[at[r]];
         g2[r] = 0;
-        l_own[r] = 0.f;
-        u[r] = 0.f;
-        total[r] = 0.f;
-        bool classB = false;
-        if (valid[r]) {
-            const uint32_t at = pos + kVsR * lane + r;
-            row[r] = P.row_begin + sorted_rows[at];
-            g[r] = P.g2p[P.assign_pos[at]];
-            classB = (g[r] == amax);
-            if (classB ? skip_b : skip_a) valid[r] = false;
+    }
+    const bool skip_a = band;
+    const bool skip_b =
+        !band && n_band_ids != 0
+        && uniform_load(&T.band_mode[T.band_by_chunk ? my_chunk : x]) != 0;
+    SlaveView v = P.feat[0];
+    v.kind = KIND;
+    const int K = P.dev ? uniform_load(&P.dev->K) : P.K;
+    const float shift = uniform_load(&P.scalars->shift);
+    const float M = uniform_load(&T.M[x]), mB = uniform_load(&T.mB[x]);
+    const int amax = uniform_load(&T.argmax[x]);
+    const float ea = u2f(g_tables_dev.exp_ab[0]);
+    const float eb = u2f(g_tables_dev.exp_ab[1]);
+    const float lf = KIND == DIST_GP ? fast_log_factorial(x) : 0.f;
+    // Stage 2: the groups, and the rows' words of the power tables
+    RowDrawWords w[kVsR];
+#pragma unroll
+    for (int r = 0; r < kVsR; ++r) {
+        g[r] = P.g2p[chain[r]];
+        w[r] = batch_row_draw_words(P, b[r]);
+    }
+    // Stage 3: the (value, group) cells -- k_vs_tables made them -- or the
+    // group sizes and, a trip later, the own scores' gathers; the draws'
+    // arithmetic runs under these loads
+    float l_tab[kVsR], s_own[kVsR];
+    bool defer[kVsR];
+    if (T.own) {
+#pragma unroll
+        for (int r = 0; r < kVsR; ++r) {
+            l_tab[r] = T.own[(size_t)x * T.Kpad + g[r]];
+            total[r] = shared ? T.tot[(size_t)x * T.Kpad + g[r]] : 0.f;
+            s_own[r] = 0.f;
         }
-        if (valid[r]) {
-            float s_own = 0.f, l_tab = 0.f;
-            bool defer;
-            if (T.own) {   // (k_vs_tables did this per (value, group))
-                l_tab = T.own[(size_t)x * T.Kpad + g[r]];
-                if (shared) total[r] = T.tot[(size_t)x * T.Kpad + g[r]];
-                defer = l_tab < 0.f;
-            } else {
-                const int n_g = P.counts[g[r]];
-                defer = (n_g == 1);
-                if (!defer) {
-                    s_own = vs_own_score(P, v, g[r], n_g, x, lf, shift);
-                    defer = !classB && s_own > M;   // table rounding lifted it
-                }
-            }
+#pragma unroll
+        for (int r = 0; r < kVsR; ++r) u[r] = batch_row_draw_unif01(P, w[r]);
+#pragma unroll
+        for (int r = 0; r < kVsR; ++r) defer[r] = l_tab[r] < 0.f;
+    } else {
+        int n_g[kVsR];
+#pragma unroll
+        for (int r = 0; r < kVsR; ++r) n_g[r] = P.counts[g[r]];
+#pragma unroll
+        for (int r = 0; r < kVsR; ++r) u[r] = batch_row_draw_unif01(P, w[r]);
+#pragma unroll
+        for (int r = 0; r < kVsR; ++r) {
+            // (a row alone in its group is handed over: its score is scored
+            // as if it had company and dropped)
+            s_own[r] = vs_own_score(P, v, g[r], max(n_g[r], 2), x, lf, shift);
+            // (s_own > M: table rounding lifted it)
+            defer[r] = n_g[r] == 1 || (g[r] != amax && s_own[r] > M);
+            l_tab[r] = 0.f;
+            total[r] = 0.f;
+        }
+    }
+    // classify, hand over, and keep what the rows that stay need
+#pragma unroll
+    for (int r = 0; r < kVsR; ++r) {
+        const bool classB = (g[r] == amax);
+        if (classB ? skip_b : skip_a) valid[r] = false;
+        if (valid[r] && defer[r]) {
+            // (a band tile's rows may straddle two chunks of its value)
+            const uint32_t chunk =
+                !D.chunk_counts ? 0u
+                : (band && !T.band_by_chunk)
+                    ? T.chunk_first[x]
+                          + (at[r] - T.val_start[x]) / (uint32_t)kVsApplyRows
+                    : my_chunk;
+            vs_hand_over(D, chunk, at[r]);
+            valid[r] = false;
+        }
+        if (T.own) {
+            l_own[r] = valid[r] ? l_tab[r] : 0.f;
+        } else {
+            // (rows that left: the exponential of 0, dropped)
             const float m = classB ? mB : M;
-            if (defer) {
-                const uint32_t at = pos + kVsR * lane + r;
-                // (a band tile's rows may straddle two chunks of its value)
-                const uint32_t chunk =
-                    !D.chunk_counts ? 0u
-                    : (band && !T.band_by_chunk)
-                        ? T.chunk_first[x]
-                              + (at - T.val_start[x]) / (uint32_t)kVsApplyRows
-                        : mine->chunk;
-                vs_hand_over(D, chunk, at);
-                valid[r] = false;
-            } else {
-                l_own[r] = T.own ? l_tab
-                                 : fast_exp_nonpos(s_own - m,
-                                                   g_tables_dev.exp_table, ea,
-                                                   eb);
-                u[r] = batch_row_unif01(P, row[r]);
-            }
+            const float e = fast_exp_nonpos(valid[r] ? s_own[r] - m : 0.f,
+                                            g_tables_dev.exp_table, ea, eb);
+            l_own[r] = valid[r] ? e : 0.f;
         }
+        u[r] = valid[r] ? u[r] : 0.f;
+        total[r] = valid[r] ? total[r] : 0.f;
         inA[r] = valid[r] && !classB;
         inB[r] = valid[r] && classB;
         anyA = anyA || inA[r];
@@ -1355,9 +1399,8 @@ void k_vs_sample(
 #pragma unroll
     for (int r = 0; r < kVsR; ++r) {
         if (valid[r]) {
-            const uint32_t at = pos + kVsR * lane + r;
-            P.old_packed[at] = (uint32_t)g[r];
-            P.new_packed[at] = (uint32_t)g2[r];
+            P.old_packed[at[r]] = (uint32_t)g[r];
+            P.new_packed[at[r]] = (uint32_t)g2[r];
         }
     }
 #ifdef DIST_VS_STAMPS
@@ -1705,9 +1748,9 @@ __global__ __launch_bounds__(64) void k_vs_narrow(
     const int lane = threadIdx.x;
     const uint32_t id = blockIdx.x;
     if (id >= n_tiles) return;
-    const uint32_t x = __builtin_amdgcn_readfirstlane(tiles[id].x);
-    const uint32_t pos = __builtin_amdgcn_readfirstlane(tiles[id].pos);
-    const uint32_t n = __builtin_amdgcn_readfirstlane(tiles[id].n);
+    // (wave-uniform words by scalar loads, as in k_vs_sample)
+    const VsTile tile = vs_load_tile(tiles + id);
+    const uint32_t x = tile.x, pos = tile.pos, n = tile.n;
     if (n == 0) return;
 #ifdef DIST_VS_STAMPS   // diagnostic build only (make stamps)
     unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0;
@@ -1731,47 +1774,49 @@ __global__ __launch_bounds__(64) void k_vs_narrow(
 
     SlaveView v = P.feat[0];
     v.kind = KIND;
-    const int K = sweep_K(P);
-    const float shift = P.scalars->shift;
-    const float M = T.M[x], mB = T.mB[x];
-    const int amax = T.argmax[x];
+    const int K = P.dev ? uniform_load(&P.dev->K) : P.K;
+    const float shift = uniform_load(&P.scalars->shift);
+    const float M = uniform_load(&T.M[x]), mB = uniform_load(&T.mB[x]);
+    const int amax = uniform_load(&T.argmax[x]);
     const float ea = u2f(g_tables_dev.exp_ab[0]);
     const float eb = u2f(g_tables_dev.exp_ab[1]);
     const float lf = KIND == DIST_GP ? fast_log_factorial(x) : 0.f;
 
+    // the row's set-up in k_vs_sample's stages: position -> group and the
+    // draw's table words -> the (value, group) cell; a lane without a row
+    // loads through the tile's last row and drops the result
     bool valid = (uint32_t)lane < n;
-    const uint32_t at = pos + lane;
-    int g = -1;
-    float l_own = 0.f, u = 0.f;
-    bool is_b = false;
-    if (valid) {
-        const size_t row = P.row_begin + sorted_rows[at];
-        g = P.g2p[P.assign_pos[at]];
-        is_b = (g == amax);
+    const uint32_t at = valid ? pos + lane : pos + n - 1;
+    const uint32_t b = sorted_rows[at];   // (row = P.row_begin + b)
+    const uint32_t chain = P.assign_pos[at];
+    const int g = P.g2p[chain];
+    const RowDrawWords w = batch_row_draw_words(P, b);
+    float l_own, u;
+    bool defer;
+    const bool is_b = valid && g == amax;
+    if (T.own) {   // (k_vs_tables did this per (value, group))
+        const float l_tab = T.own[(size_t)x * Kpad + g];
+        u = batch_row_draw_unif01(P, w);
+        defer = l_tab < 0.f;
+        l_own = l_tab;
+    } else {
+        const int n_g = P.counts[g];
+        u = batch_row_draw_unif01(P, w);
+        // (a row alone in its group is handed over: its score is scored as
+        // if it had company and dropped)
+        const float s_own = vs_own_score(P, v, g, max(n_g, 2), x, lf, shift);
+        // (s_own > M: table rounding lifted it)
+        defer = n_g == 1 || (g != amax && s_own > M);
         const float m = is_b ? mB : M;
-        float s_own = 0.f, l_tab = 0.f;
-        bool defer;
-        if (T.own) {   // (k_vs_tables did this per (value, group))
-            l_tab = T.own[(size_t)x * Kpad + g];
-            defer = l_tab < 0.f;
-        } else {
-            const int n_g = P.counts[g];
-            defer = (n_g == 1);
-            if (!defer) {
-                s_own = vs_own_score(P, v, g, n_g, x, lf, shift);
-                defer = !is_b && s_own > M;   // table rounding lifted it
-            }
-        }
-        if (defer) {
-            vs_hand_over(D, tiles[id].chunk, at);
-            valid = false;
-        } else {
-            l_own = T.own ? l_tab
-                          : fast_exp_nonpos(s_own - m, g_tables_dev.exp_table,
-                                            ea, eb);
-            u = batch_row_unif01(P, row);
-        }
+        l_own = fast_exp_nonpos(valid && !defer ? s_own - m : 0.f,
+                                g_tables_dev.exp_table, ea, eb);
     }
+    if (valid && defer) {
+        vs_hand_over(D, tile.chunk, at);
+        valid = false;
+    }
+    l_own = valid ? l_own : 0.f;
+    u = valid ? u : 0.f;
     const bool any_a = __any(valid && !is_b), any_b = __any(valid && is_b);
     if (!any_a && !any_b) return;
 #ifdef DIST_VS_STAMPS
