@@ -273,6 +273,14 @@ cdef extern from "distributions_hip.h" nogil:
                                const uint32_t * const *, const uint32_t *,
                                uint32_t * const *, uint32_t *, uint32_t,
                                uint64_t)
+    int dist_gibbs_sample_rows_many_dev(
+        dist_gibbs_t * const *, size_t, size_t, const uint32_t * const *,
+        const uint32_t *, uint32_t * const *, uint32_t *, uint32_t *, float *,
+        uint32_t, uint32_t, uint64_t, unsigned) nogil
+    int dist_gibbs_sample_rows_many(
+        dist_gibbs_t * const *, size_t, size_t, const uint32_t * const *,
+        const uint32_t *, uint32_t * const *, uint32_t *, uint32_t *, float *,
+        uint32_t, uint32_t, uint64_t, unsigned) nogil
     size_t dist_gibbs_group_count(const dist_gibbs_t *)
     size_t dist_gibbs_row_count(const dist_gibbs_t *)
     int dist_gibbs_counts(const dist_gibbs_t *, int *)
@@ -2216,3 +2224,146 @@ def predict_feature_many(engines, values, int target, candidates, observed,
     return (joint, base, None if mode is None else choice,
             None if mode is None else member, pj if members else None,
             pb if members else None, totals)
+
+
+def sample_rows_many_dev(engines, value_ptrs, size_t n_rows,
+                         size_t observed_ptr, out_ptrs, size_t group_ptr,
+                         size_t member_ptr, size_t base_ptr,
+                         uint32_t seed_state, uint32_t member_seed_state,
+                         draw_base=0, unsigned flags=0):
+    """Whole rows and missing cells drawn from an ensemble of M engines
+    (dist_gibbs_sample_rows_many_dev): engines = GibbsEngine objects,
+    value_ptrs is None or one device address per feature (0 for a feature no
+    row observes), observed_ptr the device address of the rows' masks or 0
+    (nothing observed), out_ptrs one device address per feature (may equal the
+    value's), group_ptr, member_ptr and base_ptr device addresses or 0."""
+    cdef size_t m = len(engines)
+    if m == 0 or engines[0] is None:
+        raise RuntimeError("sample_rows_many: no engine" if m == 0
+                           else "null engine")
+    cdef GibbsEngine first = engines[0]
+    cdef size_t nf = len(first.shareds)
+    if len(out_ptrs) != nf or (value_ptrs is not None
+                               and len(value_ptrs) != nf):
+        raise RuntimeError("one column per feature")
+    cdef const uint32_t ** cols = <const uint32_t **> malloc(
+        sizeof(void *) * (nf + 1))
+    cdef uint32_t ** outs = <uint32_t **> malloc(sizeof(void *) * (nf + 1))
+    cdef size_t i
+    cdef size_t addr
+    for i in range(nf):
+        addr = 0 if value_ptrs is None else value_ptrs[i]
+        cols[i] = <const uint32_t *> addr
+        addr = out_ptrs[i]
+        outs[i] = <uint32_t *> addr
+    cdef uint64_t db = <uint64_t> draw_base
+    cdef bint no_values = value_ptrs is None
+    cdef dist_gibbs_t ** ptrs
+    cdef int rc
+    try:
+        ptrs = _engine_ptrs(engines)
+    except Exception:
+        free(cols)
+        free(outs)
+        raise
+    with nogil:
+        rc = dist_gibbs_sample_rows_many_dev(
+            <dist_gibbs_t * const *> ptrs, m, n_rows,
+            NULL if no_values else cols, <const uint32_t *> observed_ptr,
+            outs, <uint32_t *> group_ptr, <uint32_t *> member_ptr,
+            <float *> base_ptr, seed_state, member_seed_state, db, flags)
+    free(ptrs)
+    free(cols)
+    free(outs)
+    check(rc)
+
+
+def sample_rows_many(engines, n_rows, values, observed, uint32_t seed_state,
+                     uint32_t member_seed_state, draw_base=0,
+                     unsigned flags=0):
+    """Whole rows and missing cells drawn from an ensemble of M engines, from
+    host arrays (dist_gibbs_sample_rows_many): values is None or one array per
+    feature (None for a feature no row observes), observed one uint32 mask per
+    row (required with values) or None: nothing observed, n_rows rows.
+    -> (columns, groups, members, base): one completed array per feature
+    (float32 for NormalInverseChiSq, uint32 otherwise), the drawn groups as
+    global ids of the drawn members, the members, and the ensemble's log
+    marginal of the observed cells"""
+    cdef size_t m = len(engines)
+    if m == 0 or engines[0] is None:
+        raise RuntimeError("sample_rows_many: no engine" if m == 0
+                           else "null engine")
+    cdef GibbsEngine first = engines[0]
+    cdef int n = len(first.shareds)
+    if values is not None and len(values) != n:
+        raise RuntimeError("one value column per feature")
+    if values is not None and observed is None:
+        raise RuntimeError("sample_rows_many: values need an observed mask")
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] mask
+    cdef const uint32_t * mask_p = NULL
+    cdef size_t rows
+    if observed is not None:
+        mask = np.ascontiguousarray(observed, dtype=np.uint32)
+        rows = mask.shape[0]
+        mask_p = <const uint32_t *> mask.data
+    else:
+        if n_rows is None:
+            raise RuntimeError("sample_rows_many: neither n nor a mask tells "
+                               "the number of rows")
+        rows = n_rows
+    if n_rows is not None and <size_t> n_rows != rows:
+        raise RuntimeError("one mask per row")
+    cdef const uint32_t ** cols = <const uint32_t **> malloc(
+        sizeof(void *) * (n + 1))
+    cdef uint32_t ** outs = <uint32_t **> malloc(sizeof(void *) * (n + 1))
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] w
+    cdef SharedParams s
+    words = []
+    outw = []
+    cdef int i
+    for i in range(n):
+        cols[i] = NULL
+        if values is not None and values[i] is not None:
+            s = first.shareds[i]
+            w = value_words(s.c.kind, values[i])
+            if <size_t> w.shape[0] != rows:
+                free(cols)
+                free(outs)
+                raise RuntimeError("feature columns differ in length")
+            words.append(w)
+            cols[i] = <const uint32_t *> w.data
+        w = np.zeros(max(rows, 1), np.uint32)
+        outw.append(w)
+        outs[i] = <uint32_t *> w.data
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] group = np.zeros(
+        max(rows, 1), np.uint32)
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] member = np.zeros(
+        max(rows, 1), np.uint32)
+    cdef cnp.ndarray[cnp.float32_t, ndim=1] base = np.zeros(
+        max(rows, 1), np.float32)
+    cdef uint64_t db = <uint64_t> draw_base
+    cdef bint no_values = values is None
+    cdef dist_gibbs_t ** ptrs
+    cdef int rc
+    try:
+        ptrs = _engine_ptrs(engines)
+    except Exception:
+        free(cols)
+        free(outs)
+        raise
+    with nogil:
+        rc = dist_gibbs_sample_rows_many(
+            <dist_gibbs_t * const *> ptrs, m, rows,
+            NULL if no_values else cols, mask_p, outs,
+            <uint32_t *> group.data, <uint32_t *> member.data,
+            <float *> base.data, seed_state, member_seed_state, db, flags)
+    free(ptrs)
+    free(cols)
+    free(outs)
+    check(rc)
+    out_cols = []
+    for i in range(n):
+        s = first.shareds[i]
+        w = outw[i][:rows]
+        out_cols.append(w.view(np.float32) if s.c.kind == DIST_NICH else w)
+    return out_cols, group[:rows], member[:rows], base[:rows]

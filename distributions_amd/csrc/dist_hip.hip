@@ -5354,6 +5354,12 @@ struct Gibbs {
                          + std::to_string(bad[1] & 0xFF));
     }
 
+    // Rows drawn from an ensemble of M engines (kernels_sample_many.h,
+    // sample_rows_many below): the first engine holds the call's buffers
+    DeviceBuf<SampleMember> smany_args;
+    DeviceBuf<float> smany_wb;          // [M][chunk]
+    DeviceBuf<uint32_t> smany_member;   // [chunk] unless the caller's
+
     // ---- the ranks' loop (dist_gibbs_sweep_sharded; the caller comes in by
     // GibbsRef::open(): a run the last pass left open may go on) ------------
     void sweep_sharded(dist_comm_t * c, size_t n_batches, size_t batch_rows,
@@ -5646,6 +5652,14 @@ struct Gibbs {
         float * members_joint_dev, size_t members_joint_ld,
         float * members_base_dev, size_t members_base_ld,
         float * prior_totals_out, unsigned flags);
+    // whole rows and missing cells drawn from M engines
+    // (kernels_sample_many.h; defined behind GibbsRef as well)
+    static void sample_rows_many(
+        dist_gibbs_t * const * engines, size_t m, size_t n,
+        const uint32_t * const * values_dev, const uint32_t * observed_dev,
+        uint32_t * const * out_dev, uint32_t * group_dev,
+        uint32_t * member_dev, float * base_dev, uint32_t seed_state,
+        uint32_t member_seed_state, uint64_t draw_base, unsigned flags);
 };
 
 }  // namespace dist
@@ -6160,6 +6174,190 @@ void dist::Gibbs::predict_feature_many(
                  who + ": value outside its feature's domain at row "
                      + std::to_string(bad >> 8) + ", feature "
                      + std::to_string(bad & 0xFF));
+}
+
+void dist::Gibbs::sample_rows_many(
+        dist_gibbs_t * const * engines, size_t m, size_t n,
+        const uint32_t * const * values_dev, const uint32_t * observed_dev,
+        uint32_t * const * out_dev, uint32_t * group_dev,
+        uint32_t * member_dev, float * base_dev, uint32_t seed_state,
+        uint32_t member_seed_state, uint64_t draw_base, unsigned flags) {
+    const std::string who = "sample_rows_many";
+    DIST_REQUIRE(flags == 0, who + ": unknown flag");
+    DIST_REQUIRE(m == 0 || engines, "null argument");
+    if (!m) return;
+    DIST_REQUIRE(m <= 65535, who + ": at most 65535 engines");
+    std::vector<Gibbs *> e(m);
+    for (size_t i = 0; i < m; ++i) {
+        DIST_REQUIRE(engines[i], "null engine");
+        e[i] = engines[i]->impl.read();   // (settles, stays resumable)
+        for (size_t j = 0; j < i; ++j)
+            DIST_REQUIRE(e[j] != e[i], "the same engine twice");
+        DIST_REQUIRE(e[i]->F() == e[0]->F(), "engines of one feature list");
+        for (int f = 0; f < e[0]->F(); ++f)
+            DIST_REQUIRE(e[i]->feats[f]->sh.kind == e[0]->feats[f]->sh.kind
+                             && e[i]->feats[f]->sh.dim
+                                    == e[0]->feats[f]->sh.dim,
+                         "engines of one feature list");
+        DIST_REQUIRE(e[i]->cluster == e[0]->cluster,
+                     "engines of one clustering model");
+        // the caches it reads are the frozen state's only between batches
+        DIST_REQUIRE(!e[i]->batch_open, "batch open");
+        e[i]->ex.require_whole(who.c_str());
+    }
+    if (!n) return;
+    Gibbs & first = *e[0];
+    const int F = first.F();
+    DIST_REQUIRE(out_dev != nullptr || F == 0, "null argument");
+    for (int f = 0; f < F; ++f)
+        DIST_REQUIRE(out_dev[f] != nullptr, "null output column");
+    const bool uncond = observed_dev == nullptr;
+    const bool le = first.cluster == 1;
+    size_t step = std::min(n, (size_t)first.opt.predict_chunk);
+    // (m x chunk words of scratch at the most)
+    step = std::min(step, std::max<size_t>(1, kManyScratchWords / m));
+    // (the 1-D grid: at least one item per workgroup)
+    step = std::min(step, (size_t)INT_MAX);
+
+    first.many_args.reserve(grow_capacity(m), 0);
+    first.smany_args.reserve(grow_capacity(m), 0);
+    first.smany_wb.reserve(m * step, 0);
+    if (!member_dev) first.smany_member.reserve(step, 0);
+    if (le) first.many_totals.reserve(grow_capacity(m), 0);
+    first.sample_bad.reserve(2, 0);
+    HIP_CHECK(hipMemsetAsync(first.sample_bad.p, 0xFF,
+                             2 * sizeof(unsigned long long), stream()));
+    first.ensure_pow_tables(step);
+    std::vector<SampleMember> args(m);
+    memset(args.data(), 0, m * sizeof(SampleMember));
+    // (k_predict_prior_many and k_predict_prior_totals take PredictMembers)
+    std::vector<PredictMember> prior_args(m);
+    memset(prior_args.data(), 0, m * sizeof(PredictMember));
+    size_t k_max = 0;
+    for (size_t i = 0; i < m; ++i) {
+        Gibbs & g = *e[i];
+        g.upload_maps();
+        g.ensure_pow_tables(step);
+        SampleMember & sm = args[i];
+        sm.P = g.params(0, 0, seed_state, draw_base);
+        g.prepare_base(sm.P);
+        const size_t Kn = (size_t)g.K();
+        k_max = std::max(k_max, Kn);
+        g.predict_prior.reserve(grow_capacity(Kn), 0);
+        if (uncond) g.sample_lik.reserve(grow_capacity(Kn + 1), 0);
+        for (int f = 0; f < F; ++f) {
+            const Slave & sl = *g.feats[f];
+            if (sl.sh.kind == DIST_DPD) {
+                g.sample_w[f].upload(sl.betas.data(), (size_t)sl.sh.dim);
+                sm.A.w[f] = g.sample_w[f].p;
+            } else if (sl.sh.kind == DIST_DD) {
+                sm.A.w[f] = sl.prior.p;   // the alphas
+            }
+        }
+        sm.A.prior = g.predict_prior.p;
+        sm.A.lik = g.sample_lik.p;
+        sm.A.p2g = g.d_p2g_ptr;
+        sm.A.seed_state = seed_state;
+        sm.A.bad = first.sample_bad.p;
+        sm.lik = g.sample_lik.p;
+        sm.wb = first.smany_wb.p + i * step;
+        sm.sub = le ? first.many_totals.p + i : nullptr;
+        PredictMember & pm = prior_args[i];
+        pm.P = sm.P;
+        pm.prior = g.predict_prior.p;
+        pm.total = le ? first.many_totals.p + i : nullptr;
+        pm.sub = pm.total;
+    }
+    const int per = predict_many_pick_rows(m);
+    for (size_t c0 = 0; c0 < n; c0 += step) {
+        const size_t c1 = std::min(n, c0 + step);
+        const size_t rows = c1 - c0;
+        for (size_t i = 0; i < m; ++i) {
+            SampleMember & sm = args[i];
+            for (int f = 0; f < F; ++f) {
+                sm.P.values[f] = !uncond && values_dev && values_dev[f]
+                                     ? values_dev[f] + c0 : nullptr;
+                sm.A.out[f] = out_dev[f] + c0;
+            }
+            sm.P.row_begin = 0;
+            sm.P.row_end = rows;
+            // row q draws its group with engine step draw_base + q + 1 of
+            // seed_state, whatever the chunking (the batch's own convention)
+            sm.P.seed_batch = lcg_jump(seed_state, draw_base + c0 + 1ull);
+            sm.A.observed = uncond ? nullptr : observed_dev + c0;
+            sm.A.group = group_dev ? group_dev + c0 : nullptr;
+            sm.A.row0 = (unsigned long long)(draw_base + c0);
+            sm.A.q0 = (unsigned long long)c0;
+        }
+        first.smany_args.upload(args.data(), m);
+        if (c0 == 0) {
+            first.many_args.upload(prior_args.data(), m);
+            hipLaunchKernelGGL(k_predict_prior_many,
+                               dim3(grid_for(k_max).x, (unsigned)m),
+                               dim3(kBlock), 0, stream(), first.many_args.p);
+            HIP_CHECK(hipGetLastError());
+            if (le) {
+                hipLaunchKernelGGL(k_predict_prior_totals,
+                                   grid_for(m, 64), dim3(64), 0, stream(),
+                                   first.many_args.p, (int)m);
+                HIP_CHECK(hipGetLastError());
+            }
+            if (uncond) {
+                // every member's likelihoods, and its plane filled with the
+                // one number all rows share: no phase A
+                hipLaunchKernelGGL(k_sample_prior_lik_many, dim3((unsigned)m),
+                                   dim3(kBlock), 0, stream(),
+                                   first.smany_args.p, step);
+                HIP_CHECK(hipGetLastError());
+            }
+        }
+        if (!uncond) {
+            hipLaunchKernelGGL(k_sample_base_many,
+                               dim3(grid_for(rows).x, (unsigned)m),
+                               dim3(kBlock), 0, stream(), first.smany_args.p);
+            HIP_CHECK(hipGetLastError());
+        }
+        EnsembleFold fold;
+        memset(&fold, 0, sizeof(fold));
+        fold.w = first.smany_wb.p;
+        fold.ld = step;
+        fold.m = (int)m;
+        fold.items = rows;
+        fold.logp = base_dev ? base_dev + c0 : nullptr;
+        fold.member = member_dev ? member_dev + c0 : first.smany_member.p;
+        fold.mode = 0;
+        fold.seed_batch = lcg_jump(member_seed_state, draw_base + c0 + 1ull);
+        fold.pow_lo = first.pow_lo.p;
+        fold.pow_hi = first.pow_hi.p;
+        LAUNCH(k_ensemble_fold, rows, fold);
+        const dim3 grid((unsigned)((rows + per - 1) / per), (unsigned)m);
+        if (uncond)
+            launch_lds<&k_sample_rows_pick<true>>(
+                grid, dim3(kBlock), predict_many_pick_lds(per),
+                first.smany_args.p, fold.member, per);
+        else
+            launch_lds<&k_sample_rows_pick<false>>(
+                grid, dim3(kBlock), predict_many_pick_lds(per),
+                first.smany_args.p, fold.member, per);
+    }
+    // the call's one wait: the two error words
+    char * pinned = chain_pinned(64);
+    HIP_CHECK(hipMemcpyAsync(pinned, first.sample_bad.p,
+                             2 * sizeof(unsigned long long),
+                             hipMemcpyDeviceToHost, stream()));
+    HIP_CHECK(hipStreamSynchronize(stream()));
+    unsigned long long bad[2] = {0, 0};
+    memcpy(bad, pinned, sizeof(bad));
+    DIST_REQUIRE(bad[0] == ~0ull,
+                 who + ": observed value outside its feature's domain (or in "
+                       "a column that was not given) at row "
+                     + std::to_string(bad[0] >> 8) + ", feature "
+                     + std::to_string(bad[0] & 0xFF));
+    DIST_REQUIRE(bad[1] == ~0ull,
+                 who + ": a cell's bounded draw ran out of tries (NaN or "
+                       "degenerate hyper-parameters?) at row "
+                     + std::to_string(bad[1] >> 8) + ", feature "
+                     + std::to_string(bad[1] & 0xFF));
 }
 
 extern "C" {
@@ -7510,6 +7708,70 @@ int dist_gibbs_sample_rows(dist_gibbs_t * g, size_t n_rows,
         for (int f = 0; f < F && n_rows; ++f)
             cols[f].download(out[f], n_rows);
         if (group_out) group.download(group_out, n_rows);
+    });
+}
+int dist_gibbs_sample_rows_many_dev(
+        dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+        const uint32_t * const * values_dev, const uint32_t * observed_dev,
+        uint32_t * const * out_dev, uint32_t * group_dev,
+        uint32_t * member_dev, float * base_dev, uint32_t seed_state,
+        uint32_t member_seed_state, uint64_t draw_base, unsigned flags) {
+    return guarded([&] {
+        Gibbs::sample_rows_many(engines, m, n_rows, values_dev, observed_dev,
+                                out_dev, group_dev, member_dev, base_dev,
+                                seed_state, member_seed_state, draw_base,
+                                flags);
+    });
+}
+int dist_gibbs_sample_rows_many(
+        dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+        const uint32_t * const * values, const uint32_t * observed,
+        uint32_t * const * out, uint32_t * group_out, uint32_t * member_out,
+        float * base_out, uint32_t seed_state, uint32_t member_seed_state,
+        uint64_t draw_base, unsigned flags) {
+    return guarded([&] {
+        DIST_REQUIRE(m == 0 || engines, "null argument");
+        // one device column per feature: the observed words go up, the
+        // completed column comes back (completion in place)
+        std::vector<DeviceBuf<uint32_t>> cols;
+        std::vector<const uint32_t *> in;
+        std::vector<uint32_t *> outp;
+        int F = 0;
+        if (m && engines[0]) {
+            F = engines[0]->impl.read()->F();
+            DIST_REQUIRE(out != nullptr || F == 0 || n_rows == 0,
+                         "null argument");
+            cols.resize((size_t)F);
+            in.assign((size_t)F, nullptr);
+            outp.assign((size_t)F, nullptr);
+            for (int f = 0; f < F && n_rows; ++f) {
+                DIST_REQUIRE(out[f] != nullptr, "null output column");
+                if (observed && values && values[f]) {
+                    cols[f].upload(values[f], n_rows);
+                    in[f] = cols[f].p;
+                } else {
+                    cols[f].reserve(n_rows, 0);
+                }
+                outp[f] = cols[f].p;
+            }
+        }
+        const size_t cells = std::max<size_t>(n_rows, 1);
+        DeviceBuf<uint32_t> mask, group, member;
+        DeviceBuf<float> base;
+        if (observed && n_rows) mask.upload(observed, n_rows);
+        if (group_out) group.reserve(cells, 0);
+        if (member_out) member.reserve(cells, 0);
+        if (base_out) base.reserve(cells, 0);
+        Gibbs::sample_rows_many(engines, m, n_rows, in.data(),
+                                observed && n_rows ? mask.p : nullptr,
+                                outp.data(), group.p, member.p, base.p,
+                                seed_state, member_seed_state, draw_base,
+                                flags);
+        if (!m || !n_rows) return;
+        for (int f = 0; f < F; ++f) cols[f].download(out[f], n_rows);
+        if (group_out) group.download(group_out, n_rows);
+        if (member_out) member.download(member_out, n_rows);
+        if (base_out) base.download(base_out, n_rows);
     });
 }
 size_t dist_gibbs_group_count(const dist_gibbs_t * g) {

@@ -29,6 +29,7 @@ constexpr size_t kLdsWorkgroupLimit = 144 * 1024;
 #include "kernels_ensemble.h"
 #include "kernels_feature.h"
 #include "kernels_sample.h"
+#include "kernels_sample_many.h"
 #include "kernels_vs.h"
 #include "kernels_apply.h"
 #include "kernels_hyper.h"

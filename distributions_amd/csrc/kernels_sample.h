@@ -132,7 +132,9 @@ struct SampleScorer {
 // UNCOND: no mask was given, the likelihoods are A.lik.  P.values are the
 // launch's query columns (null where no row observes the feature),
 // P.row_begin = 0, P.row_end the launch's row count, P.seed_batch the engine
-// state one step before the launch's first row's draw.
+// state one step before the launch's first row's draw.  The loop over the
+// rows is kernels_sample_body.h, shared with k_sample_rows_pick
+// (kernels_sample_many.h).
 template <bool UNCOND>
 __global__ __launch_bounds__(kBlock) void k_sample_rows(SweepParams P,
                                                         SampleArgs A) {
@@ -142,107 +144,15 @@ __global__ __launch_bounds__(kBlock) void k_sample_rows(SweepParams P,
             s_exp[i] = g_tables_dev.exp_table[i];
         __syncthreads();
     }
-    const float ea = u2f(g_tables_dev.exp_ab[0]);
-    const float eb = u2f(g_tables_dev.exp_ab[1]);
-    const int K = P.K, F = P.F;
-    const uint32_t fmask = F >= 32 ? ~0u : (1u << F) - 1u;
-    uint32_t nullmask = 0u;
-    for (int f = 0; f < F; ++f)
-        nullmask |= P.values[f] == nullptr ? 1u << f : 0u;
-
-    const size_t stride = (size_t)gridDim.x * kBlock;
-    const size_t n = P.row_end;
-    // whole waves iterate together so that the votes below see every lane
-    const size_t n_round = (n + 63) / 64 * 64;
-    for (size_t item = (size_t)blockIdx.x * kBlock + threadIdx.x;
-         item < n_round; item += stride) {
-        const bool live = item < n;
-        const size_t q = live ? item : 0;
-        uint32_t ob = (UNCOND || !live) ? 0u : (A.observed[q] & fmask);
-        // a feature without a column is one no row observes
-        if (ob & nullmask) {
-            atomicMin(A.bad,
-                      ((A.q0 + q) << 8) | (unsigned)(__ffs(ob & nullmask) - 1));
-            ob &= ~nullmask;
-        }
-
-        // ---- the group --------------------------------------------------
-        int g2;
-        if (UNCOND) {
-            // sample_from_likelihoods over the call's one likelihood vector
-            float t = as_uniform(A.lik)[K] * batch_row_unif01(P, q);
-            int steps = 0;
-            for (int k0 = 0; k0 < K; k0 += kSweepUnroll) {
-#pragma unroll
-                for (int j = 0; j < kSweepUnroll; ++j) {
-                    const int k = k0 + j;
-                    if (k < K) {
-                        t -= as_uniform(A.lik)[k];
-                        steps += t > 0.f ? 1 : 0;
-                    }
-                }
-                if (!__any(live && t > 0.f)) break;
-            }
-            g2 = steps < K - 1 ? steps : K - 1;
-        } else {
-            const SampleScorer sc(P, A, q, ob);
-            // vector_max (vector_math.cc:74-83)
-            float m = sc.at(0);
-#pragma unroll kSweepUnroll
-            for (int k = 1; k < K; ++k) {
-                const float s = sc.at(k);
-                m = s > m ? s : m;
-            }
-            float total = 0.f;
-#pragma unroll kSweepUnroll
-            for (int k = 0; k < K; ++k)
-                total += fast_exp_nonpos(sc.at(k) - m, s_exp, ea, eb);
-            // sample_from_likelihoods: the first index with t <= 0 is the
-            // number of steps after which t is still positive
-            float t = total * batch_row_unif01(P, q);
-            int steps = 0;
-            for (int k0 = 0; k0 < K; k0 += kSweepUnroll) {
-#pragma unroll
-                for (int j = 0; j < kSweepUnroll; ++j) {
-                    const int k = k0 + j;
-                    if (k < K) {
-                        t -= fast_exp_nonpos(sc.at(k) - m, s_exp, ea, eb);
-                        steps += t > 0.f ? 1 : 0;
-                    }
-                }
-                if (!__any(live && t > 0.f)) break;
-            }
-            g2 = steps < K - 1 ? steps : K - 1;
-        }
-        if (live && A.group != nullptr) A.group[q] = A.p2g[g2];
-
-        // ---- the cells --------------------------------------------------
-        for (int f = 0; f < F; ++f) {
-            if (!live) continue;
-            const SlaveView & v = P.feat[f];
-            uint32_t * out = A.out[f];
-            if ((ob >> f) & 1u) {
-                // an observed cell comes back as given (in place: untouched)
-                if (out != P.values[f]) out[q] = P.values[f][q];
-                continue;
-            }
-            SampleShared sh;
-            sh.kind = v.kind;
-            sh.dim = v.dim;
-            sh.p[0] = v.p[0]; sh.p[1] = v.p[1];
-            sh.p[2] = v.p[2]; sh.p[3] = v.p[3];
-            sh.w = A.w[f];
-            // the drawn group's statistics, by its packed index
-            const Stats st = {v.i0[g2], v.i1[g2], v.f0[g2], v.f1[g2]};
-            const int32_t * cnt =
-                is_cat(v.kind) ? v.cnt + (size_t)g2 * v.dim : nullptr;
-            bool exhausted = false;
-            out[q] = sample_cell_word(v.kind, sh, st, cnt, A.seed_state,
-                                      A.row0 + q, f, &exhausted);
-            if (exhausted)
-                atomicMin(A.bad + 1, ((A.q0 + q) << 8) | (unsigned)f);
-        }
-    }
+#define SAMPLE_COUNT P.row_end
+#define SAMPLE_FIRST (size_t)blockIdx.x * kBlock + threadIdx.x
+#define SAMPLE_STRIDE (size_t)gridDim.x * kBlock
+#define SAMPLE_ROW(item) item
+#include "kernels_sample_body.h"
+#undef SAMPLE_COUNT
+#undef SAMPLE_FIRST
+#undef SAMPLE_STRIDE
+#undef SAMPLE_ROW
 }
 
 }  // namespace dist

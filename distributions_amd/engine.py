@@ -523,6 +523,79 @@ def predict_feature_many_torch(engines, values, target, candidates=None,
     return joint, base, choice, chosen, pj, pb, totals
 
 
+def sample_rows_many(engines, n=None, values=None, observed=None, seed=0,
+                     member_seed=None, draw_base=0, base=False):
+    """Rows that are NOT in the table, drawn from an ensemble of M engines
+    (the chains of sweep_sequential_many, each one posterior sample): per row
+    a member first, then a group in that member, then the cells.  n, values
+    and observed are `Gibbs.sample_rows`'s.
+    -> (columns, groups, members), with base=True (columns, groups, members,
+    base):
+    members[q] is the engine drawn from p(engine | observed cells of row q),
+    proportional to p(observed cells | engine) -- `predict_feature_many`'s
+    member: the in-order fold over the engines of `Gibbs.predict_feature`'s
+    base, under LowEntropy each minus that engine's prior_total -- with engine
+    step draw_base + q + 1 of `member_seed` (None: seed + 1); groups[q] and
+    the unobserved cells of row q are what
+    engines[members[q]].sample_rows(n, values, observed, seed, draw_base)
+    gives row q, the group as that engine's global id; observed cells come
+    back as given.  base[q] = log (1/M) sum_e p(observed cells | engine e).
+    With one engine it is that engine's sample_rows.  The engines share one
+    feature list and one clustering model; nothing in them changes."""
+    if member_seed is None:
+        member_seed = seed + 1
+    cols, groups, members, b = _core.sample_rows_many(
+        _cores(engines), n, None if values is None else list(values),
+        observed, _core.rng_seed(seed), _core.rng_seed(member_seed),
+        draw_base)
+    return (cols, groups, members, b) if base else (cols, groups, members)
+
+
+def sample_rows_many_torch(engines, n=None, values=None, observed=None,
+                           seed=0, member_seed=None, draw_base=0, out=None,
+                           base=False):
+    """sample_rows_many for device tensors (values: one 4-byte-per-row CUDA
+    tensor per feature or None; observed a CUDA int32 tensor or None): the
+    results are tensors on the same device (the current one when nothing is
+    given) and nothing is staged through the host.  out: the tensors to fill,
+    one per feature; out[f] may be values[f] itself, which completes the rows
+    in place (only unobserved cells are written).
+    -> (columns, groups, members), with base=True (..., base)"""
+    import torch
+    if member_seed is None:
+        member_seed = seed + 1
+    if values is not None and observed is None:
+        raise RuntimeError("sample_rows_many: values need an observed mask")
+    if observed is not None:
+        observed = observed.contiguous()
+        n = int(observed.numel())
+        dev = observed.device
+    else:
+        values = None
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if values is not None:
+        values = [None if v is None else v.contiguous() for v in values]
+    if out is None:
+        out = [torch.empty(n, dtype=torch.float32
+                           if s.kind == _core.KIND_NICH else torch.int32,
+                           device=dev) for s in engines[0].shareds]
+    groups = torch.empty(n, dtype=torch.int32, device=dev)
+    members = torch.empty(n, dtype=torch.int32, device=dev)
+    b = torch.empty(n, dtype=torch.float32, device=dev) if base else None
+    # (the library works on its own stream: what filled the tensors on
+    # torch's must be done)
+    torch.cuda.current_stream(dev).synchronize()
+    _core.sample_rows_many_dev(
+        _cores(engines),
+        None if values is None
+        else [0 if v is None else int(v.data_ptr()) for v in values], n,
+        0 if observed is None else int(observed.data_ptr()),
+        [int(o.data_ptr()) for o in out], int(groups.data_ptr()),
+        int(members.data_ptr()), int(b.data_ptr()) if base else 0,
+        _core.rng_seed(seed), _core.rng_seed(member_seed), draw_base)
+    return (out, groups, members, b) if base else (out, groups, members)
+
+
 class ShardedGibbs(object):
     """Row-sharded Gibbs over the ranks of a torch.distributed process group.
 

@@ -862,6 +862,62 @@ int dist_gibbs_sample_rows(dist_gibbs_t * g, size_t n_rows,
                            uint32_t * group_out, uint32_t seed_state,
                            uint64_t draw_base);
 
+/* Held-out rows: whole rows and missing cells drawn from an ensemble of m
+ * engines -- a state first, then a group in that state, then the cells.  An
+ * extension: the reference has no such member, only the folds reused here.
+ * For query row q with mask observed[q] (dist_gibbs_sample_rows' bits;
+ * observed == NULL: nothing is observed, what an all-zero mask gives) and
+ * engine e in [0, m):
+ *   wb[e][q] = log_sum_exp (random.cc:78-92) of dist_gibbs_sample_rows'
+ *     scores[k] of row q on engine e: the fold dist_gibbs_predict_feature
+ *     calls `base` and dist_gibbs_predict_feature_many members_base, bit for
+ *     bit; under LowEntropy minus that engine's prior_total, one float
+ *     subtraction.  With every feature observed it is
+ *     dist_gibbs_predict_many's members_logp;
+ *   base[q] = log_sum_exp(wb[0..m)[q]) - fast_log((float)m): the log of
+ *     (1/m) sum_e p(x_obs | e), as dist_gibbs_predict_feature_many folds it;
+ *   member[q]: the engine drawn from wb[.][q], the posterior over the members
+ *     given the observed cells, by sample_from_scores_overwrite
+ *     (random.hpp:361-366) with engine step draw_base + q + 1 of
+ *     member_seed_state: dist_gibbs_predict_feature_many's mode-0 member for
+ *     equal arguments;
+ *   group[q] and every unobserved cell (q, f): what dist_gibbs_sample_rows on
+ *     engine member[q] gives for row q of the same call (same values,
+ *     observed, seed_state, draw_base) -- the group, that engine's global id,
+ *     with engine step draw_base + q + 1 of seed_state, the cells
+ *     (Group::sample_value, dd.hpp:188-199, bb.hpp:154-160, gp.hpp:166-172,
+ *     nich.hpp:204-210, bnb.hpp:168-174, dpd.hpp:275-305) keyed by
+ *     (seed_state, draw_base + q, f) on the drawn group's statistics.
+ *     Observed cells are returned as given.
+ * For m == 1 these are dist_gibbs_sample_rows' bits.  Results do not depend
+ * on chunking or launch geometry.
+ * values, observed, out: dist_gibbs_sample_rows' conventions and failures (an
+ * observed value outside its domain, a cell whose bounded loop ran out: each
+ * names the first such row and its feature, over all members); out[f] may be
+ * values[f] (completion in place).  group, member and base may be NULL.  The
+ * engines are distinct and share one feature list (kinds and dim) and one
+ * clustering model, at most 65535 of them.  A pure reader of every engine
+ * under dist_gibbs_predict_many's rules: a run a sweep left open stays
+ * resumable, an open batch or stale cells on any engine are refused.  m == 0
+ * or n_rows == 0 does nothing.  flags must be 0.  Scratch: m x chunk words for
+ * wb (chunk keeps them under 1 GiB and is at most the first engine's
+ * "debug.predict_chunk").  One host wait per call.
+ * _dev: engines, values_dev and out_dev (F device pointers each) are host
+ * arrays; observed_dev, group_dev, member_dev and base_dev are device
+ * pointers.  The host form stages, calls and downloads. */
+int dist_gibbs_sample_rows_many_dev(
+    dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+    const uint32_t * const * values_dev, const uint32_t * observed_dev,
+    uint32_t * const * out_dev, uint32_t * group_dev, uint32_t * member_dev,
+    float * base_dev, uint32_t seed_state, uint32_t member_seed_state,
+    uint64_t draw_base, unsigned flags);
+int dist_gibbs_sample_rows_many(
+    dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+    const uint32_t * const * values, const uint32_t * observed,
+    uint32_t * const * out, uint32_t * group_out, uint32_t * member_out,
+    float * base_out, uint32_t seed_state, uint32_t member_seed_state,
+    uint64_t draw_base, unsigned flags);
+
 size_t dist_gibbs_group_count(const dist_gibbs_t * g);     /* counts().size() */
 size_t dist_gibbs_row_count(const dist_gibbs_t * g);
 int dist_gibbs_counts(const dist_gibbs_t * g, int * out);  /* driver counts() */
