@@ -244,6 +244,27 @@ cdef extern from "distributions_hip.h" nogil:
                                 uint32_t *, uint32_t *, int, uint32_t,
                                 uint32_t, uint64_t, float *, size_t, float *,
                                 unsigned) nogil
+    int dist_gibbs_coassign_many_dev(dist_gibbs_t * const *, size_t, size_t,
+                                     const uint32_t * const *, size_t,
+                                     const uint32_t * const *, float *,
+                                     size_t) nogil
+    int dist_gibbs_coassign_many(dist_gibbs_t * const *, size_t, size_t,
+                                 const uint32_t * const *, size_t,
+                                 const uint32_t * const *, float *,
+                                 size_t) nogil
+    int dist_gibbs_coassign_dev(dist_gibbs_t *, size_t,
+                                const uint32_t * const *, size_t,
+                                const uint32_t * const *, float *,
+                                size_t) nogil
+    int dist_gibbs_coassign(dist_gibbs_t *, size_t, const uint32_t * const *,
+                            size_t, const uint32_t * const *, float *,
+                            size_t) nogil
+    int dist_gibbs_responsibilities_dev(dist_gibbs_t *, size_t,
+                                        const uint32_t * const *, float *,
+                                        size_t) nogil
+    int dist_gibbs_responsibilities(dist_gibbs_t *, size_t,
+                                    const uint32_t * const *, float *,
+                                    size_t) nogil
     int dist_gibbs_predict_feature_dev(dist_gibbs_t *, size_t,
                                        const uint32_t * const *,
                                        const uint32_t *, int,
@@ -2067,6 +2088,182 @@ def predict_many(engines, values, mode, uint32_t seed_state,
     return (logp, None if mode is None else member,
             None if mode is None else group, planes if members else None,
             totals)
+
+
+cdef const uint32_t ** _address_columns(value_ptrs) except NULL:
+    """a malloc'ed array of device addresses (one column per feature)"""
+    cdef size_t nf = len(value_ptrs)
+    cdef const uint32_t ** cols = <const uint32_t **> malloc(
+        sizeof(void *) * (nf + 1))
+    cdef size_t i
+    cdef size_t addr
+    for i in range(nf):
+        try:
+            addr = value_ptrs[i]
+        except Exception:
+            free(cols)
+            raise
+        cols[i] = <const uint32_t *> addr
+    return cols
+
+
+def _word_columns(GibbsEngine first, values):
+    """values as one contiguous uint32 array per feature of `first`
+    -> (arrays, rows)"""
+    cdef int n = len(first.shareds)
+    if len(values) != n:
+        raise RuntimeError("one value column per feature")
+    cdef SharedParams s
+    cdef int i
+    words = []
+    rows = 0
+    for i in range(n):
+        s = first.shareds[i]
+        w = value_words(s.c.kind, values[i])
+        if i and w.shape[0] != rows:
+            raise RuntimeError("feature columns differ in length")
+        rows = w.shape[0]
+        words.append(w)
+    return words, rows
+
+
+def coassign_many_dev(engines, q_ptrs, size_t n_q, t_ptrs, size_t n_t,
+                      size_t out_ptr, size_t ld, bint single=False):
+    """Co-assignment of row pairs over M engines
+    (dist_gibbs_coassign_many_dev; single: dist_gibbs_coassign_dev on the one
+    engine): q_ptrs / t_ptrs device addresses of one column per feature
+    (t_ptrs None: the targets are the queries), out_ptr the device address of
+    [n_q, ld] floats."""
+    cdef size_t m = len(engines)
+    if single and m != 1:
+        raise RuntimeError("coassign: one engine")
+    if m == 0 or engines[0] is None:
+        raise RuntimeError("coassign_many: no engine" if m == 0
+                           else "null engine")
+    cdef GibbsEngine first = engines[0]
+    if len(q_ptrs) != len(first.shareds) or (
+            t_ptrs is not None and len(t_ptrs) != len(first.shareds)):
+        raise RuntimeError("one value column per feature")
+    cdef const uint32_t ** qc = _address_columns(q_ptrs)
+    cdef const uint32_t ** tc = NULL
+    cdef dist_gibbs_t ** ptrs
+    cdef int rc
+    try:
+        if t_ptrs is not None:
+            tc = _address_columns(t_ptrs)
+        ptrs = _engine_ptrs(engines)
+    except Exception:
+        free(qc)
+        free(tc)
+        raise
+    with nogil:
+        if single:
+            rc = dist_gibbs_coassign_dev(ptrs[0], n_q, qc, n_t, tc,
+                                         <float *> out_ptr, ld)
+        else:
+            rc = dist_gibbs_coassign_many_dev(
+                <dist_gibbs_t * const *> ptrs, m, n_q, qc, n_t, tc,
+                <float *> out_ptr, ld)
+    free(ptrs)
+    free(qc)
+    free(tc)
+    check(rc)
+
+
+def coassign_many(engines, values, other=None, bint single=False):
+    """Co-assignment of row pairs over M engines from host arrays
+    (dist_gibbs_coassign_many; single: dist_gibbs_coassign): values and
+    other are one array per feature; other None: the targets are the
+    queries.  -> float32 [n_q, n_t]"""
+    cdef size_t m = len(engines)
+    if m == 0 or engines[0] is None:
+        raise RuntimeError("coassign_many: no engine" if m == 0
+                           else "null engine")
+    if single and m != 1:
+        raise RuntimeError("coassign: one engine")
+    cdef GibbsEngine first = engines[0]
+    qw, rows_q = _word_columns(first, values)
+    tw, rows_t = (None, rows_q) if other is None else _word_columns(first,
+                                                                    other)
+    cdef size_t nf = len(qw)
+    cdef size_t n_q = rows_q, n_t = rows_t
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] w
+    cdef cnp.ndarray[cnp.float32_t, ndim=2] out = np.zeros((n_q, n_t),
+                                                           np.float32)
+    cdef const uint32_t ** qc = <const uint32_t **> malloc(
+        sizeof(void *) * (nf + 1))
+    cdef const uint32_t ** tc = NULL
+    cdef size_t i
+    for i in range(nf):
+        w = qw[i]
+        qc[i] = <const uint32_t *> w.data
+    if tw is not None:
+        tc = <const uint32_t **> malloc(sizeof(void *) * (nf + 1))
+        for i in range(nf):
+            w = tw[i]
+            tc[i] = <const uint32_t *> w.data
+    cdef dist_gibbs_t ** ptrs
+    cdef int rc
+    try:
+        ptrs = _engine_ptrs(engines)
+    except Exception:
+        free(qc)
+        free(tc)
+        raise
+    with nogil:
+        if single:
+            rc = dist_gibbs_coassign(ptrs[0], n_q, qc, n_t, tc,
+                                     <float *> out.data, n_t)
+        else:
+            rc = dist_gibbs_coassign_many(
+                <dist_gibbs_t * const *> ptrs, m, n_q, qc, n_t, tc,
+                <float *> out.data, n_t)
+    free(ptrs)
+    free(qc)
+    free(tc)
+    check(rc)
+    return out
+
+
+def responsibilities_dev(GibbsEngine engine, value_ptrs, size_t n_rows,
+                         size_t resp_ptr, size_t ld):
+    """One engine's group posterior of held-out rows
+    (dist_gibbs_responsibilities_dev): resp_ptr the device address of
+    [groups, ld] floats, k-major."""
+    if len(value_ptrs) != len(engine.shareds):
+        raise RuntimeError("one value column per feature")
+    cdef const uint32_t ** cols = _address_columns(value_ptrs)
+    cdef int rc
+    with nogil:
+        rc = dist_gibbs_responsibilities_dev(engine.ptr, n_rows, cols,
+                                             <float *> resp_ptr, ld)
+    free(cols)
+    check(rc)
+
+
+def responsibilities(GibbsEngine engine, values):
+    """One engine's group posterior of held-out rows from host arrays
+    (dist_gibbs_responsibilities) -> float32 [groups, n], k-major"""
+    words, rows = _word_columns(engine, values)
+    cdef size_t nf = len(words)
+    cdef size_t n = rows
+    cdef size_t groups = engine.group_count()
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] w
+    cdef cnp.ndarray[cnp.float32_t, ndim=2] resp = np.zeros((groups, n),
+                                                            np.float32)
+    cdef const uint32_t ** cols = <const uint32_t **> malloc(
+        sizeof(void *) * (nf + 1))
+    cdef size_t i
+    for i in range(nf):
+        w = words[i]
+        cols[i] = <const uint32_t *> w.data
+    cdef int rc
+    with nogil:
+        rc = dist_gibbs_responsibilities(engine.ptr, n, cols,
+                                         <float *> resp.data, n)
+    free(cols)
+    check(rc)
+    return resp
 
 
 def predict_feature_many_dev(engines, value_ptrs, size_t n_rows,

@@ -5035,6 +5035,64 @@ struct Gibbs {
         }
     };
 
+    // Co-assignment of row pairs over M engines (kernels_coassign.h,
+    // coassign_many below): the first engine holds the call's buffers
+    DeviceBuf<PredictMember> co_args_q, co_args_t;
+    DeviceBuf<float> co_planes_q, co_planes_t;   // member e's [K2_e][rows]
+    struct CoassignRespLaunch {
+        const PredictMember * args;
+        unsigned m;
+        size_t ld, rows_pad;
+        int pad_k;
+        template <int KA, int KB, int NF>
+        void run() {
+            hipLaunchKernelGGL((k_coassign_resp<KA, KB, NF>),
+                               dim3(grid_for(rows_pad).x, m), dim3(kBlock), 0,
+                               stream(), args, ld, rows_pad, pad_k);
+            HIP_CHECK(hipGetLastError());
+        }
+    };
+    // phase A of coassign_many and responsibilities: rows [c0, c0 + rows) of
+    // `values` against every member, member i's plane at planes + offs[i] *
+    // ld (offs in k rows); uploads `args` into `buf`
+    static void coassign_resp(const std::vector<Gibbs *> & e,
+                              std::vector<PredictMember> & args,
+                              DeviceBuf<PredictMember> & buf,
+                              const uint32_t * const * values, size_t c0,
+                              size_t rows, float * planes,
+                              const std::vector<size_t> & offs, size_t ld,
+                              size_t rows_pad, int pad_k, bool prior,
+                              unsigned long long * bad) {
+        Gibbs & first = *e[0];
+        const size_t m = e.size();
+        size_t k_max = 0;
+        for (size_t i = 0; i < m; ++i) {
+            PredictMember & pm = args[i];
+            for (int f = 0; f < first.F(); ++f)
+                pm.P.values[f] = values[f] + c0;
+            pm.P.row_begin = 0;
+            pm.P.row_end = rows;
+            pm.A.prior = pm.prior;
+            pm.A.p2g = e[i]->d_p2g_ptr;
+            pm.A.logp = planes + offs[i] * ld;
+            pm.A.group = nullptr;
+            pm.A.mode = 1;
+            pm.A.q0 = (unsigned long long)c0;
+            pm.A.bad = bad;
+            pm.B = pm.A;
+            k_max = std::max(k_max, (size_t)pm.P.K);
+        }
+        buf.upload(args.data(), m);
+        if (prior) {
+            hipLaunchKernelGGL(k_predict_prior_many,
+                               dim3(grid_for(k_max).x, (unsigned)m),
+                               dim3(kBlock), 0, stream(), buf.p);
+            HIP_CHECK(hipGetLastError());
+        }
+        CoassignRespLaunch A{buf.p, (unsigned)m, ld, rows_pad, pad_k};
+        first.dispatch(A);
+    }
+
     // One feature's predictive given the others (kernels_feature.h)
     DeviceBuf<uint32_t> feature_cand;
     DeviceBuf<float> feature_joint;   // [chunk][C]: choice without joint
@@ -5660,6 +5718,19 @@ struct Gibbs {
         uint32_t * const * out_dev, uint32_t * group_dev,
         uint32_t * member_dev, float * base_dev, uint32_t seed_state,
         uint32_t member_seed_state, uint64_t draw_base, unsigned flags);
+    // co-assignment of row pairs over M engines and one engine's
+    // responsibilities (kernels_coassign.h; defined behind GibbsRef as well)
+    static std::vector<Gibbs *> coassign_engines(
+        dist_gibbs_t * const * engines, size_t m, const std::string & who);
+    static void coassign_many(dist_gibbs_t * const * engines, size_t m,
+                              size_t n_q,
+                              const uint32_t * const * values_q_dev,
+                              size_t n_t,
+                              const uint32_t * const * values_t_dev,
+                              float * out_dev, size_t ld);
+    static void responsibilities(dist_gibbs_t * g, size_t n,
+                                 const uint32_t * const * values_dev,
+                                 float * resp_dev, size_t ld);
 };
 
 }  // namespace dist
@@ -5946,6 +6017,190 @@ void dist::Gibbs::predict_many(dist_gibbs_t * const * engines, size_t m,
         memcpy(prior_totals_out, pinned + 64, m * sizeof(float));
     DIST_REQUIRE(bad == ~0ull,
                  "predict_many: value outside its feature's domain at row "
+                     + std::to_string(bad >> 8) + ", feature "
+                     + std::to_string(bad & 0xFF));
+}
+
+// predict_many's rules for the engines of a call
+std::vector<dist::Gibbs *> dist::Gibbs::coassign_engines(
+        dist_gibbs_t * const * engines, size_t m, const std::string & who) {
+    DIST_REQUIRE(m <= 65535, who + ": at most 65535 engines");
+    std::vector<Gibbs *> e(m);
+    for (size_t i = 0; i < m; ++i) {
+        DIST_REQUIRE(engines[i], "null engine");
+        e[i] = engines[i]->impl.read();   // (settles, stays resumable)
+        for (size_t j = 0; j < i; ++j)
+            DIST_REQUIRE(e[j] != e[i], "the same engine twice");
+        DIST_REQUIRE(e[i]->F() == e[0]->F(), "engines of one feature list");
+        for (int f = 0; f < e[0]->F(); ++f)
+            DIST_REQUIRE(e[i]->feats[f]->sh.kind == e[0]->feats[f]->sh.kind
+                             && e[i]->feats[f]->sh.dim
+                                    == e[0]->feats[f]->sh.dim,
+                         "engines of one feature list");
+        DIST_REQUIRE(e[i]->cluster == e[0]->cluster,
+                     "engines of one clustering model");
+        // the caches it reads are the frozen state's only between batches
+        DIST_REQUIRE(!e[i]->batch_open, "batch open");
+        e[i]->ex.require_whole(who.c_str());
+    }
+    return e;
+}
+
+// what phase A needs of every member but the launch's rows and planes
+static std::vector<PredictMember> coassign_members(
+        const std::vector<dist::Gibbs *> & e) {
+    std::vector<PredictMember> args(e.size());
+    memset(args.data(), 0, e.size() * sizeof(PredictMember));
+    for (size_t i = 0; i < e.size(); ++i) {
+        dist::Gibbs & g = *e[i];
+        g.upload_maps();
+        PredictMember & pm = args[i];
+        pm.P = g.params(0, 0, 0, 0);
+        g.prepare_base(pm.P);
+        g.predict_prior.reserve(grow_capacity((size_t)g.K()), 0);
+        pm.prior = g.predict_prior.p;
+    }
+    return args;
+}
+
+void dist::Gibbs::coassign_many(dist_gibbs_t * const * engines, size_t m,
+                                size_t n_q,
+                                const uint32_t * const * values_q_dev,
+                                size_t n_t,
+                                const uint32_t * const * values_t_dev,
+                                float * out_dev, size_t ld) {
+    const std::string who = "coassign_many";
+    DIST_REQUIRE(m == 0 || engines, "null argument");
+    if (!m) return;
+    const std::vector<Gibbs *> e = coassign_engines(engines, m, who);
+    const bool sym = values_t_dev == nullptr;
+    if (sym) n_t = n_q;
+    if (!n_q || !n_t) return;
+    Gibbs & first = *e[0];
+    const int F = first.F();
+    DIST_REQUIRE(out_dev != nullptr && (values_q_dev != nullptr || F == 0),
+                 "null argument");
+    for (int f = 0; f < F; ++f)
+        DIST_REQUIRE(values_q_dev[f] != nullptr
+                         && (sym || values_t_dev[f] != nullptr),
+                     "null value column");
+    DIST_REQUIRE(ld >= n_t, who + ": ld is less than the column count");
+    // member i's planes begin offs[i] k rows into the call's
+    std::vector<size_t> offs(m);
+    size_t k_rows = 0;
+    for (size_t i = 0; i < m; ++i) {
+        offs[i] = k_rows;
+        k_rows += (size_t)coassign_pad_k(e[i]->K());
+    }
+    // the rows of a launch: both operands' planes stay under 1 GiB together
+    size_t step = std::min(std::max(n_q, n_t), (size_t)first.opt.predict_chunk);
+    const size_t fit = kManyScratchWords / 2 / k_rows;
+    DIST_REQUIRE(fit >= (size_t)kCoTile,
+                 who + ": the engines' groups leave no room for a tile of "
+                       "rows in 1 GiB of scratch");
+    if (coassign_pad_rows(step) > fit) step = fit / kCoTile * kCoTile;
+    // (a grid dimension holds 65 535 tiles)
+    step = std::min(step, (size_t)65535 * kCoTile);
+    const size_t ldp = coassign_pad_rows(step);
+    first.co_planes_q.reserve(k_rows * ldp, 0);
+    if (!sym || step < n_q) first.co_planes_t.reserve(k_rows * ldp, 0);
+    first.co_args_q.reserve(grow_capacity(m), 0);
+    first.co_args_t.reserve(grow_capacity(m), 0);
+    first.predict_bad.reserve(2, 0);
+    HIP_CHECK(hipMemsetAsync(first.predict_bad.p, 0xFF,
+                             2 * sizeof(unsigned long long), stream()));
+    std::vector<PredictMember> args_q = coassign_members(e);
+    std::vector<PredictMember> args_t = args_q;
+    unsigned long long * const bad_q = first.predict_bad.p;
+    unsigned long long * const bad_t = sym ? bad_q : bad_q + 1;
+    for (size_t cq = 0; cq < n_q; cq += step) {
+        const size_t rows_q = std::min(n_q, cq + step) - cq;
+        coassign_resp(e, args_q, first.co_args_q, values_q_dev, cq, rows_q,
+                      first.co_planes_q.p, offs, ldp,
+                      coassign_pad_rows(rows_q), 1, cq == 0, bad_q);
+        // the targets are the queries: blocks left of the diagonal are the
+        // mirrors of those above it (the factors of a product commute, the
+        // chain's order is the same), written by the launch of their twin
+        for (size_t ct = sym ? cq : 0; ct < n_t; ct += step) {
+            const size_t rows_t = std::min(n_t, ct + step) - ct;
+            // ... and this is their own block: one set of planes, tiles
+            // below its diagonal mirrored as well
+            const bool diag = sym && ct == cq;
+            if (!diag)
+                coassign_resp(e, args_t, first.co_args_t,
+                              sym ? values_q_dev : values_t_dev, ct, rows_t,
+                              first.co_planes_t.p, offs, ldp,
+                              coassign_pad_rows(rows_t), 1, false, bad_t);
+            CoassignGemm G;
+            memset(&G, 0, sizeof(G));
+            G.q = first.co_args_q.p;
+            G.t = diag ? first.co_args_q.p : first.co_args_t.p;
+            G.m = (int)m;
+            G.sym = diag ? 1 : 0;
+            G.ldq = ldp;
+            G.ldt = ldp;
+            G.n_q = rows_q;
+            G.n_t = rows_t;
+            G.out = out_dev + cq * ld + ct;
+            G.mirror = sym ? out_dev + ct * ld + cq : nullptr;
+            G.ld = ld;
+            G.fm = (float)m;
+            launch_lds<&k_coassign_gemm>(
+                dim3((unsigned)(coassign_pad_rows(rows_t) / kCoTile),
+                     (unsigned)(coassign_pad_rows(rows_q) / kCoTile)),
+                dim3(kBlock), coassign_gemm_lds(), G);
+        }
+    }
+    // the call's one wait: the words of the bad values
+    char * pinned = chain_pinned(64);
+    HIP_CHECK(hipMemcpyAsync(pinned, first.predict_bad.p,
+                             2 * sizeof(unsigned long long),
+                             hipMemcpyDeviceToHost, stream()));
+    HIP_CHECK(hipStreamSynchronize(stream()));
+    unsigned long long bad[2];
+    memcpy(bad, pinned, sizeof(bad));
+    DIST_REQUIRE(bad[0] == ~0ull,
+                 who + ": value outside its feature's domain at row "
+                     + std::to_string(bad[0] >> 8) + ", feature "
+                     + std::to_string(bad[0] & 0xFF));
+    DIST_REQUIRE(bad[1] == ~0ull,
+                 who + ": value outside its feature's domain at target row "
+                     + std::to_string(bad[1] >> 8) + ", feature "
+                     + std::to_string(bad[1] & 0xFF));
+}
+
+void dist::Gibbs::responsibilities(dist_gibbs_t * g, size_t n,
+                                   const uint32_t * const * values_dev,
+                                   float * resp_dev, size_t ld) {
+    const std::string who = "responsibilities";
+    DIST_REQUIRE(g, "null engine");
+    const std::vector<Gibbs *> e = coassign_engines(&g, 1, who);
+    if (!n) return;
+    Gibbs & first = *e[0];
+    const int F = first.F();
+    DIST_REQUIRE(resp_dev != nullptr && (values_dev != nullptr || F == 0),
+                 "null argument");
+    for (int f = 0; f < F; ++f)
+        DIST_REQUIRE(values_dev[f] != nullptr, "null value column");
+    DIST_REQUIRE(ld >= n, who + ": ld is less than the row count");
+    const size_t step = std::min(n, (size_t)first.opt.predict_chunk);
+    first.co_args_q.reserve(grow_capacity(1), 0);
+    first.predict_bad.reserve(2, 0);
+    HIP_CHECK(hipMemsetAsync(first.predict_bad.p, 0xFF,
+                             sizeof(unsigned long long), stream()));
+    std::vector<PredictMember> args = coassign_members(e);
+    const std::vector<size_t> offs(1, 0);
+    for (size_t c0 = 0; c0 < n; c0 += step) {
+        const size_t rows = std::min(n, c0 + step) - c0;
+        // the caller's array is the plane: no padding in rows or in k
+        coassign_resp(e, args, first.co_args_q, values_dev, c0, rows,
+                      resp_dev + c0, offs, ld, rows, 0, c0 == 0,
+                      first.predict_bad.p);
+    }
+    unsigned long long bad = 0;
+    first.predict_bad.download(&bad, 1);   // (waits for the work)
+    DIST_REQUIRE(bad == ~0ull,
+                 who + ": value outside its feature's domain at row "
                      + std::to_string(bad >> 8) + ", feature "
                      + std::to_string(bad & 0xFF));
 }
@@ -7505,6 +7760,113 @@ int dist_gibbs_predict_many(dist_gibbs_t * const * engines, size_t m,
                                        hipMemcpyDeviceToHost, stream()));
             dist::sync();
         }
+    });
+}
+int dist_gibbs_coassign_many_dev(dist_gibbs_t * const * engines, size_t m,
+                                 size_t n_q,
+                                 const uint32_t * const * values_q_dev,
+                                 size_t n_t,
+                                 const uint32_t * const * values_t_dev,
+                                 float * out_dev, size_t ld) {
+    return guarded([&] {
+        Gibbs::coassign_many(engines, m, n_q, values_q_dev, n_t, values_t_dev,
+                             out_dev, ld);
+    });
+}
+int dist_gibbs_coassign_many(dist_gibbs_t * const * engines, size_t m,
+                             size_t n_q, const uint32_t * const * values_q,
+                             size_t n_t, const uint32_t * const * values_t,
+                             float * out, size_t ld) {
+    return guarded([&] {
+        DIST_REQUIRE(m == 0 || engines, "null argument");
+        const bool sym = values_t == nullptr;
+        if (sym) n_t = n_q;
+        std::vector<DeviceBuf<uint32_t>> cols;
+        // (never empty: a null values_t means "the targets are the queries")
+        std::vector<const uint32_t *> ptrs_q(1), ptrs_t(1);
+        const bool work = m && engines[0] && n_q && n_t;
+        if (work) {
+            const int F = engines[0]->impl.read()->F();
+            DIST_REQUIRE(values_q != nullptr || F == 0, "null argument");
+            cols.resize((size_t)F * 2);
+            ptrs_q.resize((size_t)F + 1);
+            ptrs_t.resize((size_t)F + 1);
+            for (int f = 0; f < F; ++f) {
+                DIST_REQUIRE(values_q[f] != nullptr
+                                 && (sym || values_t[f] != nullptr),
+                             "null value column");
+                cols[f].upload(values_q[f], n_q);
+                ptrs_q[f] = cols[f].p;
+                if (!sym) {
+                    cols[F + f].upload(values_t[f], n_t);
+                    ptrs_t[f] = cols[F + f].p;
+                }
+            }
+            DIST_REQUIRE(out != nullptr, "null argument");
+            DIST_REQUIRE(ld >= n_t,
+                         "coassign_many: ld is less than the column count");
+        }
+        DeviceBuf<float> cells;
+        if (work) cells.reserve(n_q * n_t, 0);
+        Gibbs::coassign_many(engines, m, n_q, ptrs_q.data(), n_t,
+                             sym ? nullptr : ptrs_t.data(), cells.p, n_t);
+        if (!work) return;
+        HIP_CHECK(hipMemcpy2DAsync(out, ld * sizeof(float), cells.p,
+                                   n_t * sizeof(float), n_t * sizeof(float),
+                                   n_q, hipMemcpyDeviceToHost, stream()));
+        dist::sync();
+    });
+}
+int dist_gibbs_coassign_dev(dist_gibbs_t * g, size_t n_q,
+                            const uint32_t * const * values_q_dev, size_t n_t,
+                            const uint32_t * const * values_t_dev,
+                            float * out_dev, size_t ld) {
+    return dist_gibbs_coassign_many_dev(&g, 1, n_q, values_q_dev, n_t,
+                                        values_t_dev, out_dev, ld);
+}
+int dist_gibbs_coassign(dist_gibbs_t * g, size_t n_q,
+                        const uint32_t * const * values_q, size_t n_t,
+                        const uint32_t * const * values_t, float * out,
+                        size_t ld) {
+    return dist_gibbs_coassign_many(&g, 1, n_q, values_q, n_t, values_t, out,
+                                    ld);
+}
+int dist_gibbs_responsibilities_dev(dist_gibbs_t * g, size_t n_rows,
+                                    const uint32_t * const * values_dev,
+                                    float * resp_dev, size_t ld) {
+    return guarded([&] {
+        Gibbs::responsibilities(g, n_rows, values_dev, resp_dev, ld);
+    });
+}
+int dist_gibbs_responsibilities(dist_gibbs_t * g, size_t n_rows,
+                                const uint32_t * const * values, float * resp,
+                                size_t ld) {
+    return guarded([&] {
+        DIST_REQUIRE(g, "null engine");
+        Gibbs * e = g->impl.read();
+        const int F = e->F();
+        const size_t K = (size_t)e->K();
+        std::vector<DeviceBuf<uint32_t>> cols((size_t)F);
+        std::vector<const uint32_t *> ptrs((size_t)F);
+        DIST_REQUIRE(values != nullptr || F == 0 || n_rows == 0,
+                     "null argument");
+        for (int f = 0; f < F && n_rows; ++f) {
+            DIST_REQUIRE(values[f] != nullptr, "null value column");
+            cols[f].upload(values[f], n_rows);
+            ptrs[f] = cols[f].p;
+        }
+        DIST_REQUIRE(!n_rows || resp != nullptr, "null argument");
+        DIST_REQUIRE(ld >= n_rows,
+                     "responsibilities: ld is less than the row count");
+        DeviceBuf<float> planes;
+        if (n_rows) planes.reserve(K * n_rows, 0);
+        Gibbs::responsibilities(g, n_rows, ptrs.data(), planes.p, n_rows);
+        if (!n_rows) return;
+        HIP_CHECK(hipMemcpy2DAsync(resp, ld * sizeof(float), planes.p,
+                                   n_rows * sizeof(float),
+                                   n_rows * sizeof(float), K,
+                                   hipMemcpyDeviceToHost, stream()));
+        dist::sync();
     });
 }
 int dist_gibbs_predict_feature_dev(dist_gibbs_t * g, size_t n_rows,

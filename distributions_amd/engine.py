@@ -174,6 +174,40 @@ class Gibbs(object):
             0 if m is None else m, _core.rng_seed(seed), draw_base)
         return logp, groups, total
 
+    def responsibilities(self, values):
+        """The group posterior of rows that are NOT in the table -> float32
+        [n, K], K = len(self): row q's `predict` scores through
+        scores_to_likelihoods (random.cc:94-103), each likelihood times
+        1.0f / total, the weights `predict(mode="sample")` draws row q's
+        group with, slot by slot (empty groups included; a slot's global id
+        is not part of it).  Nothing in the engine changes."""
+        return _core.responsibilities(self.core, list(values)).T
+
+    def responsibilities_torch(self, values):
+        """responsibilities for device tensors -> a [n, K] tensor on the same
+        device (a transposed view of the k-major planes the kernel writes)"""
+        import torch
+        values = _device_columns(values)
+        n = int(values[0].numel())
+        dev = values[0].device
+        resp = torch.empty((len(self), n), dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        _core.responsibilities_dev(self.core,
+                                   [int(v.data_ptr()) for v in values], n,
+                                   int(resp.data_ptr()), n)
+        return resp.t()
+
+    def coassign(self, values, other=None):
+        """coassign_many on this engine alone (dist_gibbs_coassign):
+        out[a, b] = sum_k r_a[k] r_b[k] with r = `responsibilities`."""
+        return _core.coassign_many([self.core], list(values),
+                                   None if other is None else list(other),
+                                   True)
+
+    def coassign_torch(self, values, other=None):
+        """coassign for device tensors -> a [n, n_other] tensor"""
+        return _coassign_torch([self], values, other, True)
+
     def predict_feature(self, values, target, candidates=None, observed=None,
                         mode="map", seed=0, draw_base=0, staged=True):
         """Given some cells of rows that are NOT in the table, the cell that
@@ -430,6 +464,68 @@ def predict_many_torch(engines, values, mode="sample", seed=0,
         _core.rng_seed(member_seed), draw_base,
         int(planes.data_ptr()) if planes is not None else 0, n, True, flags)
     return logp, chosen, groups, planes, totals
+
+
+def coassign_many(engines, values, other=None):
+    """Which rows belong together: for rows that are NOT in the table, the
+    probability that `predict(mode="sample")` puts row a of `values` and row
+    b of `other` (None: of `values` itself) into the same slot when the
+    engine is drawn uniformly from `engines` and the two draws are
+    independent.  -> float32 [n, n_other]:
+    out[a, b] = (1/M) sum_e sum_k r_e,a[k] r_e,b[k], r_e = engine e's
+    `responsibilities`, as ONE float fmaf chain per cell (engines in order,
+    slots in order) divided by float(M); with other=None symmetric bit for
+    bit.  It is NOT the joint law in which a joining a group changes b's
+    predictive, and empty slots count as distinct groups: with several empty
+    groups the new-group mass divides among them.  Cells of a row whose logp
+    is not finite are unspecified.  The engines share one feature list and
+    one clustering model; nothing in them changes."""
+    return _core.coassign_many(_cores(engines), list(values),
+                               None if other is None else list(other))
+
+
+def _device_columns(values, dev=None):
+    """device tensors as the library reads them: contiguous, 4 bytes per
+    row, one length, all on one CUDA device (`dev` if given)"""
+    values = [v.contiguous() for v in values]
+    if not values:
+        raise RuntimeError("one value column per feature")
+    dev = values[0].device if dev is None else dev
+    for v in values:
+        if not v.is_cuda or v.device != dev:
+            raise RuntimeError("value columns on one CUDA device")
+        if v.element_size() != 4:
+            raise RuntimeError("value columns of 4 bytes per row")
+        if v.numel() != values[0].numel():
+            raise RuntimeError("feature columns differ in length")
+    return values
+
+
+def _coassign_torch(engines, values, other, single):
+    import torch
+    values = _device_columns(values)
+    n_q = int(values[0].numel())
+    dev = values[0].device
+    t_ptrs, n_t = None, n_q
+    if other is not None:
+        other = _device_columns(other, dev)
+        n_t = int(other[0].numel())
+        t_ptrs = [int(v.data_ptr()) for v in other]
+    out = torch.empty((n_q, n_t), dtype=torch.float32, device=dev)
+    # (the library works on its own stream: what filled the tensors on
+    # torch's must be done)
+    torch.cuda.current_stream(dev).synchronize()
+    _core.coassign_many_dev(_cores(engines),
+                            [int(v.data_ptr()) for v in values], n_q, t_ptrs,
+                            n_t, int(out.data_ptr()), n_t, single)
+    return out
+
+
+def coassign_many_torch(engines, values, other=None):
+    """coassign_many for device tensors (one 4-byte-per-row CUDA tensor per
+    feature) -> a [n, n_other] tensor on the same device; nothing is staged
+    through the host."""
+    return _coassign_torch(engines, values, other, False)
 
 
 def predict_feature_many(engines, values, target, candidates=None,

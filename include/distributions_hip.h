@@ -668,6 +668,69 @@ int dist_gibbs_predict_many(dist_gibbs_t * const * engines, size_t m,
                             size_t members_ld, float * prior_totals_out,
                             unsigned flags);
 
+/* Held-out rows: co-assignment of row pairs over M engines, the similarity
+ * behind search, de-duplication and consensus clustering across chains.  An
+ * extension: the reference has no such member, only the pieces reused here.
+ * For engine e in [0, m) and row a, scores[k], the maximum mx and total are
+ * exactly dist_gibbs_predict's (scores_to_likelihoods, random.cc:94-103: the
+ * maximum, the in-order float sum of fast_exp(scores[k] - mx)), k in [0,
+ * dist_gibbs_group_count of e), empty groups included.  Then
+ *   r_e,a[k] = fast_exp(scores[k] - mx) * (1.0f / total): one IEEE float
+ *     division per row and one float multiply per group, subnormal results
+ *     flushed to zero.  The normalisation is per engine, so LowEntropy needs
+ *     nothing more (no prior_total);
+ *   acc[a][b] = fmaf(r_e,a[k], r_e,b[k], acc[a][b]) from 0.0f: ONE chain per
+ *     cell, engines ascending, k ascending within an engine; a the query row,
+ *     b the target row;
+ *   out[a * ld + b] = acc[a][b] / (float)m, IEEE division (ld >= n_t).
+ * This is the probability that dist_gibbs_predict with mode 0 puts rows a and
+ * b into the same slot when the engine is drawn uniformly and the two draws
+ * are independent.  It is NOT the joint law in which a joining a group changes
+ * b's predictive, and empty slots count as distinct groups: with several empty
+ * groups the new-group mass divides among them.  Cells of a row whose logp is
+ * not finite (DirichletProcessDiscrete OTHER with beta0 = 0) are unspecified.
+ * values_t == NULL: the targets are the queries, n_t is ignored and the
+ * result is symmetric bit for bit.  The engines are distinct and share one
+ * feature list and one clustering model, as for dist_gibbs_predict_many, and
+ * the calls are pure readers under its rules: a run a sweep left open stays
+ * resumable, an open batch or stale cells on any engine are refused, a value
+ * outside its domain fails the call naming the first such row and its feature
+ * ("target row" for one of values_t).  m == 0, n_q == 0 or n_t == 0 does
+ * nothing.  Scratch: the engines' responsibilities of a chunk of rows, k-major,
+ * under 1 GiB; chunk at most the first engine's "debug.predict_chunk"; results
+ * do not depend on it or on the launch geometry.  One host wait per call.
+ * dist_gibbs_coassign is the m == 1 form.
+ * dist_gibbs_responsibilities writes resp[k * ld + q] = r[k] of row q on
+ * engine g (k-major, ld >= n_rows, dist_gibbs_group_count rows of it): the
+ * group posterior of a held-out row, and the first phase of the calls above on
+ * its own.
+ * _dev: device pointers throughout (engines and values_*_dev are host
+ * arrays).  The host forms stage, call and download. */
+int dist_gibbs_coassign_many_dev(dist_gibbs_t * const * engines, size_t m,
+                                 size_t n_q,
+                                 const uint32_t * const * values_q_dev,
+                                 size_t n_t,
+                                 const uint32_t * const * values_t_dev,
+                                 float * out_dev, size_t ld);
+int dist_gibbs_coassign_many(dist_gibbs_t * const * engines, size_t m,
+                             size_t n_q, const uint32_t * const * values_q,
+                             size_t n_t, const uint32_t * const * values_t,
+                             float * out, size_t ld);
+int dist_gibbs_coassign_dev(dist_gibbs_t * g, size_t n_q,
+                            const uint32_t * const * values_q_dev, size_t n_t,
+                            const uint32_t * const * values_t_dev,
+                            float * out_dev, size_t ld);
+int dist_gibbs_coassign(dist_gibbs_t * g, size_t n_q,
+                        const uint32_t * const * values_q, size_t n_t,
+                        const uint32_t * const * values_t, float * out,
+                        size_t ld);
+int dist_gibbs_responsibilities_dev(dist_gibbs_t * g, size_t n_rows,
+                                    const uint32_t * const * values_dev,
+                                    float * resp_dev, size_t ld);
+int dist_gibbs_responsibilities(dist_gibbs_t * g, size_t n_rows,
+                                const uint32_t * const * values, float * resp,
+                                size_t ld);
+
 /* Held-out rows: one feature's predictive given the others.  For query row q,
  * a target feature t, candidate words cand[0..C) for t and a mask observed[q]
  * (bit f set: feature f of row q is observed; bit t is ignored; observed ==
