@@ -259,6 +259,22 @@ cdef extern from "distributions_hip.h" nogil:
     int dist_gibbs_coassign(dist_gibbs_t *, size_t, const uint32_t * const *,
                             size_t, const uint32_t * const *, float *,
                             size_t) nogil
+    int dist_gibbs_coassign_topk_many_dev(
+        dist_gibbs_t * const *, size_t, size_t, const uint32_t * const *,
+        size_t, const uint32_t * const *, size_t, unsigned, uint32_t *,
+        float *, size_t) nogil
+    int dist_gibbs_coassign_topk_many(
+        dist_gibbs_t * const *, size_t, size_t, const uint32_t * const *,
+        size_t, const uint32_t * const *, size_t, unsigned, uint32_t *,
+        float *, size_t) nogil
+    int dist_gibbs_coassign_topk_dev(
+        dist_gibbs_t *, size_t, const uint32_t * const *, size_t,
+        const uint32_t * const *, size_t, unsigned, uint32_t *, float *,
+        size_t) nogil
+    int dist_gibbs_coassign_topk(
+        dist_gibbs_t *, size_t, const uint32_t * const *, size_t,
+        const uint32_t * const *, size_t, unsigned, uint32_t *, float *,
+        size_t) nogil
     int dist_gibbs_responsibilities_dev(dist_gibbs_t *, size_t,
                                         const uint32_t * const *, float *,
                                         size_t) nogil
@@ -2223,6 +2239,116 @@ def coassign_many(engines, values, other=None, bint single=False):
     free(tc)
     check(rc)
     return out
+
+
+COASSIGN_EXCLUDE_SELF = 1
+
+
+def coassign_topk_many_dev(engines, q_ptrs, size_t n_q, t_ptrs, size_t n_t,
+                           size_t k, unsigned flags, size_t index_ptr,
+                           size_t prob_ptr, size_t ld, bint single=False):
+    """Per query the k most co-assigned targets over M engines
+    (dist_gibbs_coassign_topk_many_dev; single: dist_gibbs_coassign_topk_dev
+    on the one engine): q_ptrs / t_ptrs as coassign_many_dev's, index_ptr and
+    prob_ptr the device addresses of [n_q, ld] uint32 words and floats."""
+    cdef size_t m = len(engines)
+    if single and m != 1:
+        raise RuntimeError("coassign_topk: one engine")
+    if m == 0 or engines[0] is None:
+        raise RuntimeError("coassign_topk_many: no engine" if m == 0
+                           else "null engine")
+    cdef GibbsEngine first = engines[0]
+    if len(q_ptrs) != len(first.shareds) or (
+            t_ptrs is not None and len(t_ptrs) != len(first.shareds)):
+        raise RuntimeError("one value column per feature")
+    cdef const uint32_t ** qc = _address_columns(q_ptrs)
+    cdef const uint32_t ** tc = NULL
+    cdef dist_gibbs_t ** ptrs
+    cdef int rc
+    try:
+        if t_ptrs is not None:
+            tc = _address_columns(t_ptrs)
+        ptrs = _engine_ptrs(engines)
+    except Exception:
+        free(qc)
+        free(tc)
+        raise
+    with nogil:
+        if single:
+            rc = dist_gibbs_coassign_topk_dev(
+                ptrs[0], n_q, qc, n_t, tc, k, flags, <uint32_t *> index_ptr,
+                <float *> prob_ptr, ld)
+        else:
+            rc = dist_gibbs_coassign_topk_many_dev(
+                <dist_gibbs_t * const *> ptrs, m, n_q, qc, n_t, tc, k, flags,
+                <uint32_t *> index_ptr, <float *> prob_ptr, ld)
+    free(ptrs)
+    free(qc)
+    free(tc)
+    check(rc)
+
+
+def coassign_topk_many(engines, values, other, size_t k, unsigned flags,
+                       bint single=False, ld=None):
+    """Per query the k most co-assigned targets over M engines from host
+    arrays (dist_gibbs_coassign_topk_many; single: dist_gibbs_coassign_topk):
+    values and other as coassign_many's; ld: the row stride handed to the
+    library (None: k).  -> (uint32 [n_q, k], float32 [n_q, k])"""
+    cdef size_t m = len(engines)
+    if m == 0 or engines[0] is None:
+        raise RuntimeError("coassign_topk_many: no engine" if m == 0
+                           else "null engine")
+    if single and m != 1:
+        raise RuntimeError("coassign_topk: one engine")
+    cdef GibbsEngine first = engines[0]
+    qw, rows_q = _word_columns(first, values)
+    tw, rows_t = (None, rows_q) if other is None else _word_columns(first,
+                                                                    other)
+    cdef size_t nf = len(qw)
+    cdef size_t n_q = rows_q, n_t = rows_t
+    cdef size_t stride = k if ld is None else ld
+    # (a stride below k is the library's to refuse: room for k all the same)
+    cdef size_t width = max(stride, k)
+    cdef cnp.ndarray[cnp.uint32_t, ndim=2] index = np.zeros((n_q, width),
+                                                            np.uint32)
+    cdef cnp.ndarray[cnp.float32_t, ndim=2] prob = np.zeros((n_q, width),
+                                                            np.float32)
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] w
+    cdef const uint32_t ** qc = <const uint32_t **> malloc(
+        sizeof(void *) * (nf + 1))
+    cdef const uint32_t ** tc = NULL
+    cdef size_t i
+    for i in range(nf):
+        w = qw[i]
+        qc[i] = <const uint32_t *> w.data
+    if tw is not None:
+        tc = <const uint32_t **> malloc(sizeof(void *) * (nf + 1))
+        for i in range(nf):
+            w = tw[i]
+            tc[i] = <const uint32_t *> w.data
+    cdef dist_gibbs_t ** ptrs
+    cdef int rc
+    try:
+        ptrs = _engine_ptrs(engines)
+    except Exception:
+        free(qc)
+        free(tc)
+        raise
+    with nogil:
+        if single:
+            rc = dist_gibbs_coassign_topk(
+                ptrs[0], n_q, qc, n_t, tc, k, flags,
+                <uint32_t *> index.data, <float *> prob.data, stride)
+        else:
+            rc = dist_gibbs_coassign_topk_many(
+                <dist_gibbs_t * const *> ptrs, m, n_q, qc, n_t, tc, k, flags,
+                <uint32_t *> index.data, <float *> prob.data, stride)
+    free(ptrs)
+    free(qc)
+    free(tc)
+    check(rc)
+    return (np.ascontiguousarray(index[:, :k]),
+            np.ascontiguousarray(prob[:, :k]))
 
 
 def responsibilities_dev(GibbsEngine engine, value_ptrs, size_t n_rows,

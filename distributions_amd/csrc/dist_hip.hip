@@ -5039,6 +5039,9 @@ struct Gibbs {
     // coassign_many below): the first engine holds the call's buffers
     DeviceBuf<PredictMember> co_args_q, co_args_t;
     DeviceBuf<float> co_planes_q, co_planes_t;   // member e's [K2_e][rows]
+    // coassign_topk_many (kernels_coassign_topk.h): a launch's candidate keys
+    // and the call's running keys [n_q][k]
+    DeviceBuf<unsigned long long> co_topk_cand, co_topk_run;
     struct CoassignRespLaunch {
         const PredictMember * args;
         unsigned m;
@@ -5728,6 +5731,14 @@ struct Gibbs {
                               size_t n_t,
                               const uint32_t * const * values_t_dev,
                               float * out_dev, size_t ld);
+    static void coassign_topk_many(dist_gibbs_t * const * engines, size_t m,
+                                   size_t n_q,
+                                   const uint32_t * const * values_q_dev,
+                                   size_t n_t,
+                                   const uint32_t * const * values_t_dev,
+                                   size_t k, unsigned flags,
+                                   uint32_t * index_out_dev,
+                                   float * prob_out_dev, size_t ld);
     static void responsibilities(dist_gibbs_t * g, size_t n,
                                  const uint32_t * const * values_dev,
                                  float * resp_dev, size_t ld);
@@ -6063,6 +6074,19 @@ static std::vector<PredictMember> coassign_members(
     return args;
 }
 
+// the words of the bad values, the queries' and the targets'
+static void coassign_require_domains(const std::string & who,
+                                     const unsigned long long * bad) {
+    DIST_REQUIRE(bad[0] == ~0ull,
+                 who + ": value outside its feature's domain at row "
+                     + std::to_string(bad[0] >> 8) + ", feature "
+                     + std::to_string(bad[0] & 0xFF));
+    DIST_REQUIRE(bad[1] == ~0ull,
+                 who + ": value outside its feature's domain at target row "
+                     + std::to_string(bad[1] >> 8) + ", feature "
+                     + std::to_string(bad[1] & 0xFF));
+}
+
 void dist::Gibbs::coassign_many(dist_gibbs_t * const * engines, size_t m,
                                 size_t n_q,
                                 const uint32_t * const * values_q_dev,
@@ -6159,14 +6183,171 @@ void dist::Gibbs::coassign_many(dist_gibbs_t * const * engines, size_t m,
     HIP_CHECK(hipStreamSynchronize(stream()));
     unsigned long long bad[2];
     memcpy(bad, pinned, sizeof(bad));
-    DIST_REQUIRE(bad[0] == ~0ull,
-                 who + ": value outside its feature's domain at row "
-                     + std::to_string(bad[0] >> 8) + ", feature "
-                     + std::to_string(bad[0] & 0xFF));
-    DIST_REQUIRE(bad[1] == ~0ull,
-                 who + ": value outside its feature's domain at target row "
-                     + std::to_string(bad[1] >> 8) + ", feature "
-                     + std::to_string(bad[1] & 0xFF));
+    coassign_require_domains(who, bad);
+}
+
+// coassign_many without its matrix: per query the k largest cells and their
+// targets (kernels_coassign_topk.h).  The same engines' rules, phase A, planes
+// and one wait.
+void dist::Gibbs::coassign_topk_many(dist_gibbs_t * const * engines, size_t m,
+                                     size_t n_q,
+                                     const uint32_t * const * values_q_dev,
+                                     size_t n_t,
+                                     const uint32_t * const * values_t_dev,
+                                     size_t k, unsigned flags,
+                                     uint32_t * index_out_dev,
+                                     float * prob_out_dev, size_t ld) {
+    const std::string who = "coassign_topk_many";
+    DIST_REQUIRE(m == 0 || engines, "null argument");
+    const bool sym = values_t_dev == nullptr;
+    DIST_REQUIRE((flags & ~DIST_COASSIGN_EXCLUDE_SELF) == 0,
+                 who + ": unknown flag");
+    const bool exclude = (flags & DIST_COASSIGN_EXCLUDE_SELF) != 0;
+    DIST_REQUIRE(!exclude || sym,
+                 who + ": DIST_COASSIGN_EXCLUDE_SELF needs the targets to be "
+                       "the queries");
+    DIST_REQUIRE(k <= (size_t)kCoTile, who + ": k is at most 128");
+    DIST_REQUIRE(ld >= k, who + ": ld is less than k");
+    if (!m || !k) return;
+    const std::vector<Gibbs *> e = coassign_engines(engines, m, who);
+    if (sym) n_t = n_q;
+    if (!n_q || !n_t) return;
+    DIST_REQUIRE(n_t <= 0xFFFFFFFEull, who + ": at most 2^32 - 2 targets");
+    Gibbs & first = *e[0];
+    const int F = first.F();
+    DIST_REQUIRE(index_out_dev != nullptr && prob_out_dev != nullptr
+                     && (values_q_dev != nullptr || F == 0),
+                 "null argument");
+    for (int f = 0; f < F; ++f)
+        DIST_REQUIRE(values_q_dev[f] != nullptr
+                         && (sym || values_t_dev[f] != nullptr),
+                     "null value column");
+    std::vector<size_t> offs(m);
+    size_t k_rows = 0;
+    for (size_t i = 0; i < m; ++i) {
+        offs[i] = k_rows;
+        k_rows += (size_t)coassign_pad_k(e[i]->K());
+    }
+    // the rows of a launch, as coassign_many has them ...
+    size_t step = std::min(std::max(n_q, n_t), (size_t)first.opt.predict_chunk);
+    const size_t fit = kManyScratchWords / 2 / k_rows;
+    DIST_REQUIRE(fit >= (size_t)kCoTile,
+                 who + ": the engines' groups leave no room for a tile of "
+                       "rows in 1 GiB of scratch");
+    if (coassign_pad_rows(step) > fit) step = fit / kCoTile * kCoTile;
+    step = std::min(step, (size_t)65535 * kCoTile);
+    const size_t ldp = coassign_pad_rows(step);
+    // ... and a launch's candidates (k keys per row and tile of columns; with
+    // the targets the queries the same again for its columns) under 1 GiB
+    // too: `room` is the most (tiles of rows) x (tiles of columns)
+    const int kc = (int)k;
+    size_t step_q = std::min(n_q, step), step_t = std::min(n_t, step);
+    const size_t room =
+        kManyScratchWords / 2 / ((size_t)kCoTile * k) / (sym ? 2 : 1);
+    auto tiles = [](size_t rows) { return coassign_pad_rows(rows) / kCoTile; };
+    if (tiles(step_q) * tiles(step_t) > room) {
+        if (sym) {
+            size_t side = tiles(step_q);
+            while (side * side > room) --side;
+            step_q = step_t = side * kCoTile;
+        } else {
+            // (the longer side gives way first)
+            if (tiles(step_t) >= tiles(step_q))
+                step_t = std::max<size_t>(1, room / tiles(step_q)) * kCoTile;
+            if (tiles(step_q) * tiles(step_t) > room)
+                step_q = std::max<size_t>(1, room / tiles(step_t)) * kCoTile;
+        }
+    }
+    const size_t cand_q_words =
+        coassign_pad_rows(step_q) * tiles(step_t) * (size_t)kc;
+    // (the columns' candidates of a block off the diagonal: chunked calls)
+    const size_t cand_t_words =
+        sym && step_q < n_q
+            ? coassign_pad_rows(step_t) * tiles(step_q) * (size_t)kc
+            : 0;
+    first.co_topk_cand.reserve(cand_q_words + cand_t_words, 0);
+    first.co_topk_run.reserve(n_q * k, 0);
+    HIP_CHECK(hipMemsetAsync(first.co_topk_run.p, 0,
+                             n_q * k * sizeof(unsigned long long), stream()));
+    first.co_planes_q.reserve(k_rows * ldp, 0);
+    if (!sym || step_q < n_q) first.co_planes_t.reserve(k_rows * ldp, 0);
+    first.co_args_q.reserve(grow_capacity(m), 0);
+    first.co_args_t.reserve(grow_capacity(m), 0);
+    first.predict_bad.reserve(2, 0);
+    HIP_CHECK(hipMemsetAsync(first.predict_bad.p, 0xFF,
+                             2 * sizeof(unsigned long long), stream()));
+    std::vector<PredictMember> args_q = coassign_members(e);
+    std::vector<PredictMember> args_t = args_q;
+    unsigned long long * const bad_q = first.predict_bad.p;
+    unsigned long long * const bad_t = sym ? bad_q : bad_q + 1;
+    unsigned long long * const run = first.co_topk_run.p;
+    for (size_t cq = 0; cq < n_q; cq += step_q) {
+        const size_t rows_q = std::min(n_q, cq + step_q) - cq;
+        coassign_resp(e, args_q, first.co_args_q, values_q_dev, cq, rows_q,
+                      first.co_planes_q.p, offs, ldp,
+                      coassign_pad_rows(rows_q), 1, cq == 0, bad_q);
+        // the targets are the queries: a block left of the diagonal is the
+        // transpose of its twin above it, whose launch selects along its
+        // columns for the rows here
+        for (size_t ct = sym ? cq : 0; ct < n_t; ct += step_t) {
+            const size_t rows_t = std::min(n_t, ct + step_t) - ct;
+            const bool diag = sym && ct == cq;
+            if (!diag)
+                coassign_resp(e, args_t, first.co_args_t,
+                              sym ? values_q_dev : values_t_dev, ct, rows_t,
+                              first.co_planes_t.p, offs, ldp,
+                              coassign_pad_rows(rows_t), 1, false, bad_t);
+            CoassignTopk G;
+            memset(&G, 0, sizeof(G));
+            G.q = first.co_args_q.p;
+            G.t = diag ? first.co_args_q.p : first.co_args_t.p;
+            G.m = (int)m;
+            G.sym = diag ? 1 : 0;
+            G.exclude = exclude ? 1 : 0;
+            G.kc = kc;
+            G.ldq = ldp;
+            G.ldt = ldp;
+            G.n_q = rows_q;
+            G.n_t = rows_t;
+            G.q0 = cq;
+            G.t0 = ct;
+            G.tiles_q = (unsigned)tiles(rows_q);
+            G.tiles_t = (unsigned)tiles(rows_t);
+            G.cand_q = first.co_topk_cand.p;
+            G.cand_t = !sym ? nullptr
+                       : diag ? G.cand_q
+                              : G.cand_q + cand_q_words;
+            G.fm = (float)m;
+            launch_lds<&k_coassign_topk>(dim3(G.tiles_t, G.tiles_q),
+                                         dim3(kBlock), coassign_topk_lds(),
+                                         G);
+            hipLaunchKernelGGL(k_coassign_topk_merge, dim3((unsigned)rows_q),
+                               dim3(kCoTopkMergeBlock), 0, stream(), G.cand_q,
+                               G.tiles_t, kc, (int)k, run + cq * k);
+            HIP_CHECK(hipGetLastError());
+            if (sym && !diag) {
+                hipLaunchKernelGGL(k_coassign_topk_merge,
+                                   dim3((unsigned)rows_t),
+                                   dim3(kCoTopkMergeBlock), 0, stream(),
+                                   G.cand_t, G.tiles_q, kc, (int)k,
+                                   run + ct * k);
+                HIP_CHECK(hipGetLastError());
+            }
+        }
+    }
+    hipLaunchKernelGGL(k_coassign_topk_decode, grid_for(n_q * k),
+                       dim3(kBlock), 0, stream(), run, n_q, (int)k,
+                       index_out_dev, prob_out_dev, ld);
+    HIP_CHECK(hipGetLastError());
+    // the call's one wait: the words of the bad values
+    char * pinned = chain_pinned(64);
+    HIP_CHECK(hipMemcpyAsync(pinned, first.predict_bad.p,
+                             2 * sizeof(unsigned long long),
+                             hipMemcpyDeviceToHost, stream()));
+    HIP_CHECK(hipStreamSynchronize(stream()));
+    unsigned long long bad[2];
+    memcpy(bad, pinned, sizeof(bad));
+    coassign_require_domains(who, bad);
 }
 
 void dist::Gibbs::responsibilities(dist_gibbs_t * g, size_t n,
@@ -7830,6 +8011,95 @@ int dist_gibbs_coassign(dist_gibbs_t * g, size_t n_q,
                         size_t ld) {
     return dist_gibbs_coassign_many(&g, 1, n_q, values_q, n_t, values_t, out,
                                     ld);
+}
+int dist_gibbs_coassign_topk_many_dev(dist_gibbs_t * const * engines, size_t m,
+                                      size_t n_q,
+                                      const uint32_t * const * values_q_dev,
+                                      size_t n_t,
+                                      const uint32_t * const * values_t_dev,
+                                      size_t k, unsigned flags,
+                                      uint32_t * index_out_dev,
+                                      float * prob_out_dev, size_t ld) {
+    return guarded([&] {
+        Gibbs::coassign_topk_many(engines, m, n_q, values_q_dev, n_t,
+                                  values_t_dev, k, flags, index_out_dev,
+                                  prob_out_dev, ld);
+    });
+}
+int dist_gibbs_coassign_topk_many(dist_gibbs_t * const * engines, size_t m,
+                                  size_t n_q,
+                                  const uint32_t * const * values_q,
+                                  size_t n_t,
+                                  const uint32_t * const * values_t, size_t k,
+                                  unsigned flags, uint32_t * index_out,
+                                  float * prob_out, size_t ld) {
+    return guarded([&] {
+        DIST_REQUIRE(m == 0 || engines, "null argument");
+        const bool sym = values_t == nullptr;
+        if (sym) n_t = n_q;
+        std::vector<DeviceBuf<uint32_t>> cols;
+        // (never empty: a null values_t means "the targets are the queries")
+        std::vector<const uint32_t *> ptrs_q(1), ptrs_t(1);
+        const bool work = m && engines[0] && n_q && n_t && k;
+        if (work) {
+            const int F = engines[0]->impl.read()->F();
+            DIST_REQUIRE(values_q != nullptr || F == 0, "null argument");
+            cols.resize((size_t)F * 2);
+            ptrs_q.resize((size_t)F + 1);
+            ptrs_t.resize((size_t)F + 1);
+            for (int f = 0; f < F; ++f) {
+                DIST_REQUIRE(values_q[f] != nullptr
+                                 && (sym || values_t[f] != nullptr),
+                             "null value column");
+                cols[f].upload(values_q[f], n_q);
+                ptrs_q[f] = cols[f].p;
+                if (!sym) {
+                    cols[F + f].upload(values_t[f], n_t);
+                    ptrs_t[f] = cols[F + f].p;
+                }
+            }
+            DIST_REQUIRE(index_out != nullptr && prob_out != nullptr,
+                         "null argument");
+        }
+        // (the limits on k and ld are the device form's: its ld here is k)
+        DIST_REQUIRE(ld >= k, "coassign_topk_many: ld is less than k");
+        DeviceBuf<uint32_t> index;
+        DeviceBuf<float> prob;
+        if (work && k <= (size_t)dist::kCoTile) {
+            index.reserve(n_q * k, 0);
+            prob.reserve(n_q * k, 0);
+        }
+        Gibbs::coassign_topk_many(engines, m, n_q, ptrs_q.data(), n_t,
+                                  sym ? nullptr : ptrs_t.data(), k, flags,
+                                  index.p, prob.p, k);
+        if (!work) return;
+        HIP_CHECK(hipMemcpy2DAsync(index_out, ld * sizeof(uint32_t), index.p,
+                                   k * sizeof(uint32_t), k * sizeof(uint32_t),
+                                   n_q, hipMemcpyDeviceToHost, stream()));
+        HIP_CHECK(hipMemcpy2DAsync(prob_out, ld * sizeof(float), prob.p,
+                                   k * sizeof(float), k * sizeof(float), n_q,
+                                   hipMemcpyDeviceToHost, stream()));
+        dist::sync();
+    });
+}
+int dist_gibbs_coassign_topk_dev(dist_gibbs_t * g, size_t n_q,
+                                 const uint32_t * const * values_q_dev,
+                                 size_t n_t,
+                                 const uint32_t * const * values_t_dev,
+                                 size_t k, unsigned flags,
+                                 uint32_t * index_out_dev,
+                                 float * prob_out_dev, size_t ld) {
+    return dist_gibbs_coassign_topk_many_dev(&g, 1, n_q, values_q_dev, n_t,
+                                             values_t_dev, k, flags,
+                                             index_out_dev, prob_out_dev, ld);
+}
+int dist_gibbs_coassign_topk(dist_gibbs_t * g, size_t n_q,
+                             const uint32_t * const * values_q, size_t n_t,
+                             const uint32_t * const * values_t, size_t k,
+                             unsigned flags, uint32_t * index_out,
+                             float * prob_out, size_t ld) {
+    return dist_gibbs_coassign_topk_many(&g, 1, n_q, values_q, n_t, values_t,
+                                         k, flags, index_out, prob_out, ld);
 }
 int dist_gibbs_responsibilities_dev(dist_gibbs_t * g, size_t n_rows,
                                     const uint32_t * const * values_dev,

@@ -110,13 +110,22 @@ constexpr size_t coassign_gemm_lds() {
 // LDS reads are contiguous), two k per MFMA, k ascending.
 // Operands (32x32x2): lane l holds A[i = l & 31][k = l >> 5] and
 // B[k = l >> 5][j = l & 31]; D: column = lane & 31, row = (reg & 3) +
-// 8 (reg >> 2) + 4 (lane >> 5).  Loads are unguarded (padded planes); the
-// stores are guarded by n_q and n_t.
-__global__ __launch_bounds__(kBlock) void k_coassign_gemm(CoassignGemm G) {
-    typedef float f32x16 __attribute__((ext_vector_type(16)));
-    extern __shared__ float co_lds[];
-    const unsigned it = blockIdx.y, jt = blockIdx.x;
-    if (G.sym && jt < it) return;
+// 8 (reg >> 2) + 4 (lane >> 5).  Loads are unguarded (padded planes).
+typedef float co_f32x16 __attribute__((ext_vector_type(16)));
+// what a thread is in its tile
+struct CoassignLane {
+    unsigned wi, wj;     // its wave's quarter: first row and column
+    unsigned ok, oc;     // operands: the k row within a pair and the row /
+                         // column of a sub-tile
+};
+// The contraction of tile (it, jt) of the launch, shared by k_coassign_gemm
+// and k_coassign_topk (kernels_coassign_topk.h): -> acc, the cells' chains
+// before the division.  co_lds: coassign_gemm_lds() bytes.  Ends after the
+// last MFMA's operand reads, without a barrier.
+__device__ __forceinline__ CoassignLane coassign_contract(
+        const PredictMember * q, const PredictMember * t, int m, size_t ldq,
+        size_t ldt, unsigned it, unsigned jt, float * co_lds,
+        co_f32x16 (&acc)[2][2]) {
     float * const sA = co_lds;
     float * const sB = co_lds + kCoSlab * kCoRow;
     const unsigned tid = threadIdx.x;
@@ -125,10 +134,8 @@ __global__ __launch_bounds__(kBlock) void k_coassign_gemm(CoassignGemm G) {
     const size_t i0 = (size_t)it * kCoTile, j0 = (size_t)jt * kCoTile;
     // staging: 32 threads copy one k row of a tile, four floats each
     const unsigned lr = tid >> 5, lc = (tid & 31u) * 4;
-    // operands: the k row within a pair and the row / column of a sub-tile
     const unsigned ok = lane >> 5, oc = lane & 31u;
 
-    f32x16 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -136,10 +143,10 @@ __global__ __launch_bounds__(kBlock) void k_coassign_gemm(CoassignGemm G) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 
-    for (int e = 0; e < G.m; ++e) {
-        const int K2 = coassign_pad_k(G.q[e].P.K);
-        const float * const pa = G.q[e].A.logp + i0 + lc;
-        const float * const pb = G.t[e].A.logp + j0 + lc;
+    for (int e = 0; e < m; ++e) {
+        const int K2 = coassign_pad_k(q[e].P.K);
+        const float * const pa = q[e].A.logp + i0 + lc;
+        const float * const pb = t[e].A.logp + j0 + lc;
         for (int k0 = 0; k0 < K2; k0 += kCoSlab) {
             const int h = K2 - k0 < kCoSlab ? K2 - k0 : kCoSlab;   // (even)
             __syncthreads();
@@ -148,9 +155,9 @@ __global__ __launch_bounds__(kBlock) void k_coassign_gemm(CoassignGemm G) {
                 const int kr = r + (int)lr;
                 if (kr < h) {
                     const float4 va = *reinterpret_cast<const float4 *>(
-                        pa + (size_t)(k0 + kr) * G.ldq);
+                        pa + (size_t)(k0 + kr) * ldq);
                     const float4 vb = *reinterpret_cast<const float4 *>(
-                        pb + (size_t)(k0 + kr) * G.ldt);
+                        pb + (size_t)(k0 + kr) * ldt);
                     *reinterpret_cast<float4 *>(sA + kr * kCoRow + lc) = va;
                     *reinterpret_cast<float4 *>(sB + kr * kCoRow + lc) = vb;
                 }
@@ -172,6 +179,19 @@ __global__ __launch_bounds__(kBlock) void k_coassign_gemm(CoassignGemm G) {
             }
         }
     }
+    return CoassignLane{wi, wj, ok, oc};
+}
+
+// The dense form: the stores are guarded by n_q and n_t.
+__global__ __launch_bounds__(kBlock) void k_coassign_gemm(CoassignGemm G) {
+    extern __shared__ float co_lds[];
+    const unsigned it = blockIdx.y, jt = blockIdx.x;
+    if (G.sym && jt < it) return;
+    const size_t i0 = (size_t)it * kCoTile, j0 = (size_t)jt * kCoTile;
+    co_f32x16 acc[2][2];
+    const CoassignLane L = coassign_contract(G.q, G.t, G.m, G.ldq, G.ldt, it,
+                                             jt, co_lds, acc);
+    const unsigned wi = L.wi, wj = L.wj, ok = L.ok, oc = L.oc;
 
     const bool mirror = G.mirror != nullptr && !(G.sym && jt == it);
 #pragma unroll

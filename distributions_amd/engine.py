@@ -208,6 +208,17 @@ class Gibbs(object):
         """coassign for device tensors -> a [n, n_other] tensor"""
         return _coassign_torch([self], values, other, True)
 
+    def coassign_topk(self, values, other=None, k=10, exclude_self=None):
+        """coassign_topk_many on this engine alone
+        (dist_gibbs_coassign_topk) -> (index int32 [n, k], prob [n, k])"""
+        return _coassign_topk([self], values, other, k, exclude_self, True)
+
+    def coassign_topk_torch(self, values, other=None, k=10,
+                            exclude_self=None):
+        """coassign_topk for device tensors -> two [n, k] tensors"""
+        return _coassign_topk_torch([self], values, other, k, exclude_self,
+                                    True)
+
     def predict_feature(self, values, target, candidates=None, observed=None,
                         mode="map", seed=0, draw_base=0, staged=True):
         """Given some cells of rows that are NOT in the table, the cell that
@@ -526,6 +537,67 @@ def coassign_many_torch(engines, values, other=None):
     feature) -> a [n, n_other] tensor on the same device; nothing is staged
     through the host."""
     return _coassign_torch(engines, values, other, False)
+
+
+def _coassign_topk_flags(other, exclude_self):
+    if exclude_self is None:
+        exclude_self = other is None
+    return _core.COASSIGN_EXCLUDE_SELF if exclude_self else 0
+
+
+def _coassign_topk(engines, values, other, k, exclude_self, single):
+    index, prob = _core.coassign_topk_many(
+        _cores(engines), list(values),
+        None if other is None else list(other), k,
+        _coassign_topk_flags(other, exclude_self), single)
+    return index.view(np.int32), prob
+
+
+def coassign_topk_many(engines, values, other=None, k=10, exclude_self=None):
+    """Search and de-duplication over rows that are NOT in the table: for
+    every row a of `values`, the k rows b of `other` (None: of `values`
+    itself) it most likely shares a slot with -- the k largest cells of
+    `coassign_many`'s row a, bit for bit, without the [n, n_other] matrix.
+    -> (index int32 [n, k], prob float32 [n, k]): targets by cell descending,
+    among bit-equal cells by index ascending; where fewer than k targets are
+    eligible the rest is index -1 and probability +0.  exclude_self leaves
+    b == a out; None means `other is None`, and True with `other` given fails.
+    k is at most 128.  A row of `values` whose logp is not finite has an
+    unspecified result row; such a row among the targets leaves the whole
+    result unspecified."""
+    return _coassign_topk(engines, values, other, k, exclude_self, False)
+
+
+def _coassign_topk_torch(engines, values, other, k, exclude_self, single):
+    import torch
+    values = _device_columns(values)
+    n_q = int(values[0].numel())
+    dev = values[0].device
+    t_ptrs, n_t = None, n_q
+    if other is not None:
+        other = _device_columns(other, dev)
+        n_t = int(other[0].numel())
+        t_ptrs = [int(v.data_ptr()) for v in other]
+    k = int(k)
+    index = torch.empty((n_q, k), dtype=torch.int32, device=dev)
+    prob = torch.empty((n_q, k), dtype=torch.float32, device=dev)
+    # (the library works on its own stream: what filled the tensors on
+    # torch's must be done)
+    torch.cuda.current_stream(dev).synchronize()
+    _core.coassign_topk_many_dev(
+        _cores(engines), [int(v.data_ptr()) for v in values], n_q, t_ptrs,
+        n_t, k, _coassign_topk_flags(other, exclude_self),
+        int(index.data_ptr()), int(prob.data_ptr()), k, single)
+    return index, prob
+
+
+def coassign_topk_many_torch(engines, values, other=None, k=10,
+                             exclude_self=None):
+    """coassign_topk_many for device tensors (one 4-byte-per-row CUDA tensor
+    per feature) -> (index int32 [n, k], prob float32 [n, k]) on the same
+    device; nothing is staged through the host."""
+    return _coassign_topk_torch(engines, values, other, k, exclude_self,
+                                False)
 
 
 def predict_feature_many(engines, values, target, candidates=None,

@@ -731,6 +731,65 @@ int dist_gibbs_responsibilities(dist_gibbs_t * g, size_t n_rows,
                                 const uint32_t * const * values, float * resp,
                                 size_t ld);
 
+/* Held-out rows: per query, the k targets it is most likely co-assigned with
+ * over M engines -- what search and de-duplication need of the matrix above,
+ * without the matrix.  cell(a, b) is, bit for bit, the float that
+ * dist_gibbs_coassign_many writes to out[a * ld + b] for the same engines and
+ * rows (one fmaf chain per cell, engines ascending, slots ascending, then
+ * / (float)m).
+ *   Eligible targets of query a: every b in [0, n_t); with
+ *     DIST_COASSIGN_EXCLUDE_SELF, b == a is left out.  The flag is legal only
+ *     when values_t == NULL (the targets are the queries, n_t is ignored) and
+ *     fails the call otherwise, as does any other flag bit.
+ *   Order: by cell descending, and among bit-equal cells by b ascending.  Cells
+ *     of specified rows are >= +0 and never NaN, so this is the descending
+ *     order of key = ((uint64_t)bits(cell) << 32) | (0xFFFFFFFF - b); keys of
+ *     distinct targets are distinct, so the result does not depend on tiles,
+ *     chunks, launch geometry or "debug.predict_chunk".
+ *   Output: for j < min(k, number of eligible targets), index_out[a * ld + j]
+ *     is the j-th target and prob_out[a * ld + j] its cell; for larger j < k
+ *     the entries are 0xFFFFFFFF and +0.0f (key 0, below every real key).
+ *   Limits: ld >= k and k <= 128, otherwise the call fails; k == 0, m == 0,
+ *     n_q == 0 or n_t == 0 does nothing; n_t <= 2^32 - 2.
+ * Rows with non-finite logp (dist_gibbs_coassign_many leaves their cells
+ * unspecified): a QUERY row with non-finite logp on any engine has an
+ * unspecified result row; if ANY TARGET row has non-finite logp on any engine,
+ * the whole call's result is unspecified (its cells may displace any row's
+ * targets).  Engines, readers, errors and the one host wait are
+ * dist_gibbs_coassign_many's.  Scratch: its planes, the running k keys of
+ * every query (8 k n_q bytes) and the candidate keys of one launch, under
+ * 1 GiB.  dist_gibbs_coassign_topk is the m == 1 form.
+ * _dev: device pointers throughout (engines and values_*_dev are host
+ * arrays).  The host forms stage, call and download. */
+#define DIST_COASSIGN_EXCLUDE_SELF 1u
+int dist_gibbs_coassign_topk_many_dev(dist_gibbs_t * const * engines, size_t m,
+                                      size_t n_q,
+                                      const uint32_t * const * values_q_dev,
+                                      size_t n_t,
+                                      const uint32_t * const * values_t_dev,
+                                      size_t k, unsigned flags,
+                                      uint32_t * index_out_dev,
+                                      float * prob_out_dev, size_t ld);
+int dist_gibbs_coassign_topk_many(dist_gibbs_t * const * engines, size_t m,
+                                  size_t n_q,
+                                  const uint32_t * const * values_q,
+                                  size_t n_t,
+                                  const uint32_t * const * values_t, size_t k,
+                                  unsigned flags, uint32_t * index_out,
+                                  float * prob_out, size_t ld);
+int dist_gibbs_coassign_topk_dev(dist_gibbs_t * g, size_t n_q,
+                                 const uint32_t * const * values_q_dev,
+                                 size_t n_t,
+                                 const uint32_t * const * values_t_dev,
+                                 size_t k, unsigned flags,
+                                 uint32_t * index_out_dev,
+                                 float * prob_out_dev, size_t ld);
+int dist_gibbs_coassign_topk(dist_gibbs_t * g, size_t n_q,
+                             const uint32_t * const * values_q, size_t n_t,
+                             const uint32_t * const * values_t, size_t k,
+                             unsigned flags, uint32_t * index_out,
+                             float * prob_out, size_t ld);
+
 /* Held-out rows: one feature's predictive given the others.  For query row q,
  * a target feature t, candidate words cand[0..C) for t and a mask observed[q]
  * (bit f set: feature f of row q is observed; bit t is ignored; observed ==
