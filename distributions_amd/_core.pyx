@@ -318,6 +318,22 @@ cdef extern from "distributions_hip.h" nogil:
         dist_gibbs_t * const *, size_t, size_t, const uint32_t * const *,
         const uint32_t *, uint32_t * const *, uint32_t *, uint32_t *, float *,
         uint32_t, uint32_t, uint64_t, unsigned) nogil
+    int dist_gibbs_marginals_dev(dist_gibbs_t *, size_t,
+                                 const uint32_t * const *, const uint32_t *,
+                                 size_t, float *) nogil
+    int dist_gibbs_marginals(dist_gibbs_t *, size_t, const uint32_t * const *,
+                             const uint32_t *, size_t, float *) nogil
+    int dist_gibbs_marginals_many_dev(
+        dist_gibbs_t * const *, size_t, size_t, const uint32_t * const *,
+        const uint32_t *, size_t, float *, float *, size_t, float *) nogil
+    int dist_gibbs_marginals_many(
+        dist_gibbs_t * const *, size_t, size_t, const uint32_t * const *,
+        const uint32_t *, size_t, float *, float *, size_t, float *) nogil
+    int dist_gibbs_relate(dist_gibbs_t *, size_t, uint32_t, uint32_t,
+                          uint64_t, double *, double *, double *) nogil
+    int dist_gibbs_relate_many(dist_gibbs_t * const *, size_t, size_t,
+                               uint32_t, uint32_t, uint64_t, double *,
+                               double *, double *) nogil
     size_t dist_gibbs_group_count(const dist_gibbs_t *)
     size_t dist_gibbs_row_count(const dist_gibbs_t *)
     int dist_gibbs_counts(const dist_gibbs_t *, int *)
@@ -2690,3 +2706,179 @@ def sample_rows_many(engines, n_rows, values, observed, uint32_t seed_state,
         w = outw[i][:rows]
         out_cols.append(w.view(np.float32) if s.c.kind == DIST_NICH else w)
     return out_cols, group[:rows], member[:rows], base[:rows]
+
+
+def marginals_many_dev(engines, value_ptrs, size_t n_rows, masks,
+                       size_t logp_ptr, size_t members_ptr=0,
+                       size_t members_ld=0, bint prior_totals=True,
+                       bint single=False):
+    """The log marginals of feature subsets over M engines
+    (dist_gibbs_marginals_many_dev; single: dist_gibbs_marginals_dev on the
+    one engine): engines = GibbsEngine objects, value_ptrs device addresses of
+    one column of n_rows words per feature (0 for a feature no mask names),
+    masks a host list of uint32, the other pointers device addresses or 0.
+    -> the engines' prior totals (numpy float32), or None"""
+    cdef size_t m = len(engines)
+    if m == 0 or engines[0] is None:
+        raise RuntimeError("marginals_many: no engine" if m == 0
+                           else "null engine")
+    cdef GibbsEngine first = engines[0]
+    cdef size_t nf = len(value_ptrs)
+    if nf != len(first.shareds):
+        raise RuntimeError("one value column per feature")
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] mk = np.ascontiguousarray(
+        masks, dtype=np.uint32).reshape(-1)
+    cdef size_t n_masks = mk.shape[0]
+    cdef const uint32_t * mk_p = <const uint32_t *> mk.data
+    cdef const uint32_t ** cols = <const uint32_t **> malloc(
+        sizeof(void *) * (nf + 1))
+    cdef size_t i
+    cdef size_t addr
+    for i in range(nf):
+        addr = value_ptrs[i]
+        cols[i] = <const uint32_t *> addr
+    cdef cnp.ndarray[cnp.float32_t, ndim=1] totals = np.zeros(m, np.float32)
+    cdef float * tp = <float *> totals.data if prior_totals else NULL
+    cdef dist_gibbs_t ** ptrs
+    cdef int rc
+    try:
+        ptrs = _engine_ptrs(engines)
+    except Exception:
+        free(cols)
+        raise
+    if single and m != 1:
+        free(ptrs)
+        free(cols)
+        raise RuntimeError("marginals: one engine")
+    with nogil:
+        if single:
+            rc = dist_gibbs_marginals_dev(ptrs[0], n_rows, cols, mk_p,
+                                          n_masks, <float *> logp_ptr)
+        else:
+            rc = dist_gibbs_marginals_many_dev(
+                <dist_gibbs_t * const *> ptrs, m, n_rows, cols, mk_p, n_masks,
+                <float *> logp_ptr, <float *> members_ptr, members_ld, tp)
+    free(ptrs)
+    free(cols)
+    check(rc)
+    return totals.copy() if prior_totals and not single else None
+
+
+def marginals_many(engines, values, masks, bint members=False,
+                   bint single=False):
+    """The log marginals of feature subsets over M engines, from host arrays
+    (dist_gibbs_marginals_many; single: dist_gibbs_marginals on the one
+    engine): values is one array per feature (None for a feature no mask
+    names), masks a list of uint32.
+    -> (logp [n, S], members_logp [M, n, S] or None, prior_totals [M] or
+    None)"""
+    cdef size_t m = len(engines)
+    if m == 0 or engines[0] is None:
+        raise RuntimeError("marginals_many: no engine" if m == 0
+                           else "null engine")
+    cdef GibbsEngine first = engines[0]
+    cdef int n = len(first.shareds)
+    if len(values) != n:
+        raise RuntimeError("one value column per feature")
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] mk = np.ascontiguousarray(
+        masks, dtype=np.uint32).reshape(-1)
+    cdef size_t n_masks = mk.shape[0]
+    cdef const uint32_t * mk_p = <const uint32_t *> mk.data
+    cdef const uint32_t ** cols = <const uint32_t **> malloc(
+        sizeof(void *) * (n + 1))
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] w
+    cdef SharedParams s
+    words = []
+    cdef int i
+    cdef Py_ssize_t rows = -1
+    try:
+        for i in range(n):
+            cols[i] = NULL
+            if values[i] is None:
+                continue
+            s = first.shareds[i]
+            w = value_words(s.c.kind, values[i])
+            if rows >= 0 and w.shape[0] != rows:
+                raise RuntimeError("feature columns differ in length")
+            rows = w.shape[0]
+            words.append(w)
+            cols[i] = <const uint32_t *> w.data
+        if rows < 0:
+            raise RuntimeError("marginals_many: no column tells the number "
+                               "of rows")
+    except Exception:
+        free(cols)
+        raise
+    cdef size_t n_rows = rows
+    cdef size_t cells = max(n_masks, 1)
+    cdef cnp.ndarray[cnp.float32_t, ndim=2] logp = np.zeros(
+        (rows, cells), np.float32)
+    cdef cnp.ndarray[cnp.float32_t, ndim=3] planes = np.zeros(
+        (m if members else 1, rows if members else 1,
+         cells if members else 1), np.float32)
+    cdef cnp.ndarray[cnp.float32_t, ndim=1] totals = np.zeros(m, np.float32)
+    cdef float * pp = <float *> planes.data if members else NULL
+    cdef dist_gibbs_t ** ptrs
+    cdef int rc
+    try:
+        ptrs = _engine_ptrs(engines)
+    except Exception:
+        free(cols)
+        raise
+    if single and m != 1:
+        free(ptrs)
+        free(cols)
+        raise RuntimeError("marginals: one engine")
+    with nogil:
+        if single:
+            rc = dist_gibbs_marginals(ptrs[0], n_rows, cols, mk_p, n_masks,
+                                      <float *> logp.data)
+        else:
+            rc = dist_gibbs_marginals_many(
+                <dist_gibbs_t * const *> ptrs, m, n_rows, cols, mk_p, n_masks,
+                <float *> logp.data, pp, n_rows * cells,
+                <float *> totals.data)
+    free(ptrs)
+    free(cols)
+    check(rc)
+    return (logp, planes if members else None,
+            None if single else totals)
+
+
+def relate_many(engines, size_t n_samples, uint32_t seed_state,
+                uint32_t member_seed_state, draw_base=0, bint single=False):
+    """Mutual information of every feature pair and the entropies under the
+    predictive of M engines (dist_gibbs_relate_many; single: dist_gibbs_relate
+    on the one engine) -> (mi [F, F] float64, stderr [F, F] float64,
+    moments [F, F, 2] float64: the sums of d and of d^2)"""
+    cdef size_t m = len(engines)
+    if m == 0 or engines[0] is None:
+        raise RuntimeError("relate_many: no engine" if m == 0
+                           else "null engine")
+    cdef GibbsEngine first = engines[0]
+    cdef size_t nf = len(first.shareds)
+    cdef cnp.ndarray[cnp.float64_t, ndim=2] mi = np.zeros((nf, nf),
+                                                          np.float64)
+    cdef cnp.ndarray[cnp.float64_t, ndim=2] se = np.zeros((nf, nf),
+                                                          np.float64)
+    cdef cnp.ndarray[cnp.float64_t, ndim=3] mo = np.zeros((nf, nf, 2),
+                                                          np.float64)
+    cdef uint64_t db = <uint64_t> draw_base
+    cdef dist_gibbs_t ** ptrs = _engine_ptrs(engines)
+    cdef int rc
+    if single and m != 1:
+        free(ptrs)
+        raise RuntimeError("relate: one engine")
+    with nogil:
+        if single:
+            rc = dist_gibbs_relate(ptrs[0], n_samples, seed_state,
+                                   member_seed_state, db, <double *> mi.data,
+                                   <double *> se.data, <double *> mo.data)
+        else:
+            rc = dist_gibbs_relate_many(
+                <dist_gibbs_t * const *> ptrs, m, n_samples, seed_state,
+                member_seed_state, db, <double *> mi.data, <double *> se.data,
+                <double *> mo.data)
+    free(ptrs)
+    check(rc)
+    return mi, se, mo

@@ -5327,6 +5327,55 @@ struct Gibbs {
             dim3((unsigned)g.blocks, m), dim3(kBlock), g.lds, args);
     }
 
+    // Log marginals of feature subsets over M engines and the moments of the
+    // mutual-information estimate (kernels_marginals.h, marginals_many and
+    // relate_many below): the first engine holds the call's buffers
+    DeviceBuf<MarginalsMember> mg_args;
+    DeviceBuf<uint32_t> mg_masks;     // [S]
+    DeviceBuf<float> mg_w;            // [M][chunk * S] unless the caller's
+    DeviceBuf<uint32_t> relate_cols[kMaxF];   // [chunk]: the drawn rows
+    DeviceBuf<float> relate_l;        // [chunk][S]: their folded marginals
+    DeviceBuf<double> relate_acc;     // [F * F][3]
+    // the plain form, launched when a row has one chain (k_marginals_plain)
+    struct MarginalsPlainLaunch {
+        const MarginalsMember * args;
+        unsigned m;
+        size_t items;
+        template <int KA, int KB, int NF>
+        void run() {
+            hipLaunchKernelGGL((k_marginals_plain<KA, KB, NF>),
+                               dim3(grid_for(items).x, m), dim3(kBlock), 0,
+                               stream(), args);
+            HIP_CHECK(hipGetLastError());
+        }
+    };
+    // the launch geometry of k_marginals_many, the same for every member:
+    // rows are given up before the tile falls under a wave of groups (or the
+    // call's largest K), then the largest tile under kFeatureLdsBudget
+    static FeatureGeometry marginals_geometry(size_t n_rows, size_t S,
+                                              size_t k_max, int terms) {
+        const size_t tile_min = std::min<size_t>(k_max, 64);
+        const size_t rows_fit =
+            kFeatureLdsBudget / marginals_lds(terms, (int)tile_min, 1);
+        const size_t rows_cap = std::min<size_t>(
+            (size_t)kMarginalsRowsMax, std::max<size_t>(rows_fit, 1));
+        // `items` consecutive items touch at most (items + S - 2) / S + 1 rows
+        const size_t items =
+            std::min<size_t>(kBlock, (rows_cap - 1) * S + 1);
+        int rows = (int)((items + S - 2) / S + 1);
+        rows = (int)std::min<size_t>((size_t)rows, n_rows);
+        const size_t per_k = marginals_lds(terms, 0, rows);
+        const int tile = (int)std::min<size_t>(k_max,
+                                               kFeatureLdsBudget / per_k - 1);
+        FeatureGeometry g;
+        g.items = (int)items;
+        g.rows = rows;
+        g.tile = std::max(tile, 1);
+        g.lds = marginals_lds(terms, g.tile, rows);
+        g.blocks = (n_rows * S + items - 1) / items;
+        return g;
+    }
+
     // Whole rows and missing cells drawn from the mixture (kernels_sample.h)
     DeviceBuf<float> sample_lik;      // [K + 1]: the nothing-observed instance
     DeviceBuf<float> sample_w[kMaxF]; // DPD betas
@@ -5721,6 +5770,43 @@ struct Gibbs {
         uint32_t * const * out_dev, uint32_t * group_dev,
         uint32_t * member_dev, float * base_dev, uint32_t seed_state,
         uint32_t member_seed_state, uint64_t draw_base, unsigned flags);
+    // ... its engines, validated; its launches without the wait (reset_bad:
+    // start the error words anew; row_base: the launch's first row counted
+    // from the caller's first, for the errors' report); and the wait's report
+    static std::vector<Gibbs *> sample_rows_many_engines(
+        dist_gibbs_t * const * engines, size_t m, const std::string & who);
+    static void sample_rows_many_enqueue(
+        const std::vector<Gibbs *> & e, size_t n,
+        const uint32_t * const * values_dev, const uint32_t * observed_dev,
+        uint32_t * const * out_dev, uint32_t * group_dev,
+        uint32_t * member_dev, float * base_dev, uint32_t seed_state,
+        uint32_t member_seed_state, uint64_t draw_base, bool reset_bad,
+        size_t row_base);
+    static void sample_rows_many_report(const unsigned long long * bad,
+                                        const std::string & who);
+    // log marginals of feature subsets over M engines (kernels_marginals.h;
+    // defined behind GibbsRef as well).  single: one engine and no fold.
+    static std::vector<Gibbs *> marginals_engines(
+        dist_gibbs_t * const * engines, size_t m, bool single,
+        const std::string & who);
+    static void marginals_enqueue(
+        const std::vector<Gibbs *> & e, size_t n,
+        const uint32_t * const * values_dev, const uint32_t * masks,
+        size_t n_masks, float * logp_dev, float * members_dev,
+        size_t members_ld, bool want_totals, bool single, bool reset_bad,
+        size_t row_base, const std::string & who);
+    static void marginals_many(
+        dist_gibbs_t * const * engines, size_t m, size_t n,
+        const uint32_t * const * values_dev, const uint32_t * masks,
+        size_t n_masks, float * logp_dev, float * members_dev,
+        size_t members_ld, float * prior_totals_out, bool single);
+    // mutual information of every feature pair and the entropies, estimated
+    // from rows drawn from the ensemble (kernels_marginals.h)
+    static void relate_many(dist_gibbs_t * const * engines, size_t m,
+                            size_t n_samples, uint32_t seed_state,
+                            uint32_t member_seed_state, uint64_t draw_base,
+                            double * mi_out, double * stderr_out,
+                            double * moments_out, bool single);
     // co-assignment of row pairs over M engines and one engine's
     // responsibilities (kernels_coassign.h; defined behind GibbsRef as well)
     static std::vector<Gibbs *> coassign_engines(
@@ -6620,8 +6706,41 @@ void dist::Gibbs::sample_rows_many(
         uint32_t member_seed_state, uint64_t draw_base, unsigned flags) {
     const std::string who = "sample_rows_many";
     DIST_REQUIRE(flags == 0, who + ": unknown flag");
+    const std::vector<Gibbs *> e = sample_rows_many_engines(engines, m, who);
+    if (e.empty() || !n) return;
+    Gibbs * const first = e[0];
+    sample_rows_many_enqueue(e, n, values_dev, observed_dev, out_dev,
+                             group_dev, member_dev, base_dev, seed_state,
+                             member_seed_state, draw_base, true, 0);
+    // the call's one wait: the two error words
+    char * pinned = chain_pinned(64);
+    HIP_CHECK(hipMemcpyAsync(pinned, first->sample_bad.p,
+                             2 * sizeof(unsigned long long),
+                             hipMemcpyDeviceToHost, stream()));
+    HIP_CHECK(hipStreamSynchronize(stream()));
+    unsigned long long bad[2] = {0, 0};
+    memcpy(bad, pinned, sizeof(bad));
+    sample_rows_many_report(bad, who);
+}
+
+void dist::Gibbs::sample_rows_many_report(const unsigned long long * bad,
+                                          const std::string & who) {
+    DIST_REQUIRE(bad[0] == ~0ull,
+                 who + ": observed value outside its feature's domain (or in "
+                       "a column that was not given) at row "
+                     + std::to_string(bad[0] >> 8) + ", feature "
+                     + std::to_string(bad[0] & 0xFF));
+    DIST_REQUIRE(bad[1] == ~0ull,
+                 who + ": a cell's bounded draw ran out of tries (NaN or "
+                       "degenerate hyper-parameters?) at row "
+                     + std::to_string(bad[1] >> 8) + ", feature "
+                     + std::to_string(bad[1] & 0xFF));
+}
+
+std::vector<dist::Gibbs *> dist::Gibbs::sample_rows_many_engines(
+        dist_gibbs_t * const * engines, size_t m, const std::string & who) {
     DIST_REQUIRE(m == 0 || engines, "null argument");
-    if (!m) return;
+    if (!m) return {};
     DIST_REQUIRE(m <= 65535, who + ": at most 65535 engines");
     std::vector<Gibbs *> e(m);
     for (size_t i = 0; i < m; ++i) {
@@ -6641,7 +6760,17 @@ void dist::Gibbs::sample_rows_many(
         DIST_REQUIRE(!e[i]->batch_open, "batch open");
         e[i]->ex.require_whole(who.c_str());
     }
-    if (!n) return;
+    return e;
+}
+
+void dist::Gibbs::sample_rows_many_enqueue(
+        const std::vector<Gibbs *> & e, size_t n,
+        const uint32_t * const * values_dev, const uint32_t * observed_dev,
+        uint32_t * const * out_dev, uint32_t * group_dev,
+        uint32_t * member_dev, float * base_dev, uint32_t seed_state,
+        uint32_t member_seed_state, uint64_t draw_base, bool reset_bad,
+        size_t row_base) {
+    const size_t m = e.size();
     Gibbs & first = *e[0];
     const int F = first.F();
     DIST_REQUIRE(out_dev != nullptr || F == 0, "null argument");
@@ -6661,8 +6790,9 @@ void dist::Gibbs::sample_rows_many(
     if (!member_dev) first.smany_member.reserve(step, 0);
     if (le) first.many_totals.reserve(grow_capacity(m), 0);
     first.sample_bad.reserve(2, 0);
-    HIP_CHECK(hipMemsetAsync(first.sample_bad.p, 0xFF,
-                             2 * sizeof(unsigned long long), stream()));
+    if (reset_bad)
+        HIP_CHECK(hipMemsetAsync(first.sample_bad.p, 0xFF,
+                                 2 * sizeof(unsigned long long), stream()));
     first.ensure_pow_tables(step);
     std::vector<SampleMember> args(m);
     memset(args.data(), 0, m * sizeof(SampleMember));
@@ -6723,7 +6853,7 @@ void dist::Gibbs::sample_rows_many(
             sm.A.observed = uncond ? nullptr : observed_dev + c0;
             sm.A.group = group_dev ? group_dev + c0 : nullptr;
             sm.A.row0 = (unsigned long long)(draw_base + c0);
-            sm.A.q0 = (unsigned long long)c0;
+            sm.A.q0 = (unsigned long long)(row_base + c0);
         }
         first.smany_args.upload(args.data(), m);
         if (c0 == 0) {
@@ -6776,24 +6906,304 @@ void dist::Gibbs::sample_rows_many(
                 grid, dim3(kBlock), predict_many_pick_lds(per),
                 first.smany_args.p, fold.member, per);
     }
-    // the call's one wait: the two error words
-    char * pinned = chain_pinned(64);
+}
+
+std::vector<dist::Gibbs *> dist::Gibbs::marginals_engines(
+        dist_gibbs_t * const * engines, size_t m, bool single,
+        const std::string & who) {
+    DIST_REQUIRE(engines, "null argument");
+    DIST_REQUIRE(m >= 1, who + ": no engine");
+    DIST_REQUIRE(!single || m == 1, who + ": one engine");
+    DIST_REQUIRE(m <= 65535, who + ": at most 65535 engines");
+    std::vector<Gibbs *> e(m);
+    for (size_t i = 0; i < m; ++i) {
+        DIST_REQUIRE(engines[i], "null engine");
+        e[i] = engines[i]->impl.read();   // (settles, stays resumable)
+        for (size_t j = 0; j < i; ++j)
+            DIST_REQUIRE(e[j] != e[i], "the same engine twice");
+        DIST_REQUIRE(e[i]->F() == e[0]->F(), "engines of one feature list");
+        for (int f = 0; f < e[0]->F(); ++f)
+            DIST_REQUIRE(e[i]->feats[f]->sh.kind == e[0]->feats[f]->sh.kind
+                             && e[i]->feats[f]->sh.dim
+                                    == e[0]->feats[f]->sh.dim,
+                         "engines of one feature list");
+        DIST_REQUIRE(e[i]->cluster == e[0]->cluster,
+                     "engines of one clustering model");
+        // the caches it reads are the frozen state's only between batches
+        DIST_REQUIRE(!e[i]->batch_open, "batch open");
+        e[i]->ex.require_whole(who.c_str());
+    }
+    return e;
+}
+
+// The launches of marginals_many without its wait: the members' priors (and
+// prior totals), then per chunk k_marginals_many and, unless `single`, the
+// fold.  The word of the bad values is the first engine's predict_bad, the
+// prior totals its many_totals.
+void dist::Gibbs::marginals_enqueue(
+        const std::vector<Gibbs *> & e, size_t n,
+        const uint32_t * const * values_dev, const uint32_t * masks,
+        size_t n_masks, float * logp_dev, float * members_dev,
+        size_t members_ld, bool want_totals, bool single, bool reset_bad,
+        size_t row_base, const std::string & who) {
+    const size_t m = e.size();
+    Gibbs & first = *e[0];
+    const int F = first.F();
+    // the masks, validated before any launch
+    DIST_REQUIRE(masks != nullptr && n_masks >= 1, who + ": no mask");
+    DIST_REQUIRE(n_masks < ((size_t)1 << 24), who + ": bad mask count");
+    const size_t S = n_masks;
+    uint32_t named = 0;
+    for (size_t s = 0; s < S; ++s) {
+        DIST_REQUIRE(F >= 32 || (masks[s] >> F) == 0,
+                     who + ": mask " + std::to_string(s)
+                         + " names a feature the engines do not have");
+        named |= masks[s];
+    }
+    DIST_REQUIRE(values_dev != nullptr || n == 0 || named == 0,
+                 "null argument");
+    for (size_t s = 0; s < S && n; ++s)
+        for (int f = 0; f < F; ++f)
+            DIST_REQUIRE(!((masks[s] >> f) & 1u) || values_dev[f] != nullptr,
+                         who + ": mask " + std::to_string(s)
+                             + " names feature " + std::to_string(f)
+                             + ", whose value column is null");
+    DIST_REQUIRE(!members_dev || members_ld / S >= n,
+                 who + ": members_ld is less than rows x masks");
+    const bool le = first.cluster == 1;
+    want_totals = want_totals || le;
+    float * const planes = single ? logp_dev : members_dev;
+    const bool want_w = n != 0 && (logp_dev != nullptr || planes != nullptr);
+    size_t step = std::max<size_t>(
+        1, std::min(n, (size_t)first.opt.predict_chunk));
+    // (m x chunk x S floats of scratch at the most)
+    if (!planes)
+        step = std::min(step,
+                        std::max<size_t>(1, kManyScratchWords / (m * S)));
+    // (the 1-D grid: at least one item per workgroup)
+    step = std::min(step, std::max<size_t>(1, (size_t)INT_MAX / S));
+
+    first.many_args.reserve(grow_capacity(m), 0);
+    first.mg_args.reserve(grow_capacity(m), 0);
+    if (want_w && !planes) first.mg_w.reserve(m * step * S, 0);
+    if (want_totals) first.many_totals.reserve(grow_capacity(m), 0);
+    first.predict_bad.reserve(1, 0);
+    if (reset_bad)
+        HIP_CHECK(hipMemsetAsync(first.predict_bad.p, 0xFF,
+                                 sizeof(unsigned long long), stream()));
+    first.mg_masks.upload(masks, S);
+    int terms = 0;
+    for (int f = 0; f < F; ++f)
+        if ((named >> f) & 1u)
+            terms += is_cat(first.feats[f]->sh.kind) ? 2 : 1;
+    std::vector<MarginalsMember> args(m);
+    memset(args.data(), 0, m * sizeof(MarginalsMember));
+    // (k_predict_prior_many and k_predict_prior_totals take PredictMembers)
+    std::vector<PredictMember> prior_args(m);
+    memset(prior_args.data(), 0, m * sizeof(PredictMember));
+    size_t k_max = 0;
+    for (size_t i = 0; i < m; ++i) {
+        Gibbs & g = *e[i];
+        g.upload_maps();
+        MarginalsMember & mm = args[i];
+        mm.P = g.params(0, 0, 1u, 0);
+        g.prepare_base(mm.P);
+        const size_t Kn = (size_t)g.K();
+        k_max = std::max(k_max, Kn);
+        g.predict_prior.reserve(grow_capacity(Kn), 0);
+        mm.prior = g.predict_prior.p;
+        mm.total = want_totals ? first.many_totals.p + i : nullptr;
+        mm.sub = le ? mm.total : nullptr;
+        PredictMember & pm = prior_args[i];
+        pm.P = mm.P;
+        pm.prior = mm.prior;
+        pm.total = mm.total;
+        pm.sub = mm.sub;
+    }
+    first.many_args.upload(prior_args.data(), m);
+    hipLaunchKernelGGL(k_predict_prior_many,
+                       dim3(grid_for(k_max).x, (unsigned)m), dim3(kBlock), 0,
+                       stream(), first.many_args.p);
+    HIP_CHECK(hipGetLastError());
+    if (want_totals) {
+        hipLaunchKernelGGL(k_predict_prior_totals, grid_for(m, 64), dim3(64),
+                           0, stream(), first.many_args.p, (int)m);
+        HIP_CHECK(hipGetLastError());
+    }
+    if (!want_w) return;
+    for (size_t c0 = 0; c0 < n; c0 += step) {
+        const size_t c1 = std::min(n, c0 + step);
+        const size_t rows = c1 - c0;
+        float * const w = planes ? planes + c0 * S : first.mg_w.p;
+        const size_t ld = single ? 0 : members_dev ? members_ld : step * S;
+        const FeatureGeometry geo = marginals_geometry(rows, S, k_max, terms);
+        for (size_t i = 0; i < m; ++i) {
+            MarginalsMember & mm = args[i];
+            for (int f = 0; f < F; ++f)
+                mm.P.values[f] = values_dev && values_dev[f]
+                                     ? values_dev[f] + c0 : nullptr;
+            mm.P.row_begin = 0;
+            mm.P.row_end = rows;
+            mm.A.prior = mm.prior;
+            mm.A.masks = first.mg_masks.p;
+            mm.A.S = (int)S;
+            mm.A.named = named;
+            mm.A.items = geo.items;
+            mm.A.rows = geo.rows;
+            mm.A.tile = geo.tile;
+            mm.A.out = w + i * ld;
+            mm.A.q0 = (unsigned long long)(row_base + c0);
+            mm.A.bad = first.predict_bad.p;
+        }
+        first.mg_args.upload(args.data(), m);
+        if (S == 1) {
+            // one chain per row: nothing to stage once and share
+            MarginalsPlainLaunch plain{first.mg_args.p, (unsigned)m, rows * S};
+            first.dispatch(plain);
+        } else {
+            launch_lds<&k_marginals_many>(
+                dim3((unsigned)geo.blocks, (unsigned)m), dim3(kBlock), geo.lds,
+                first.mg_args.p);
+        }
+        if (single || logp_dev == nullptr) continue;
+        EnsembleFold fold;
+        memset(&fold, 0, sizeof(fold));
+        fold.w = w;
+        fold.ld = ld;
+        fold.m = (int)m;
+        fold.items = rows * S;
+        fold.logp = logp_dev + c0 * S;
+        LAUNCH(k_ensemble_fold, rows * S, fold);
+    }
+}
+
+void dist::Gibbs::marginals_many(
+        dist_gibbs_t * const * engines, size_t m, size_t n,
+        const uint32_t * const * values_dev, const uint32_t * masks,
+        size_t n_masks, float * logp_dev, float * members_dev,
+        size_t members_ld, float * prior_totals_out, bool single) {
+    const std::string who = single ? "marginals" : "marginals_many";
+    const std::vector<Gibbs *> e = marginals_engines(engines, m, single, who);
+    Gibbs & first = *e[0];
+    marginals_enqueue(e, n, values_dev, masks, n_masks, logp_dev, members_dev,
+                      members_ld, prior_totals_out != nullptr, single, true,
+                      0, who);
+    // the call's one wait: the word of the bad values and the prior totals
+    char * pinned = chain_pinned(64 + m * sizeof(float));
+    HIP_CHECK(hipMemcpyAsync(pinned, first.predict_bad.p,
+                             sizeof(unsigned long long),
+                             hipMemcpyDeviceToHost, stream()));
+    if (prior_totals_out)
+        HIP_CHECK(hipMemcpyAsync(pinned + 64, first.many_totals.p,
+                                 m * sizeof(float), hipMemcpyDeviceToHost,
+                                 stream()));
+    HIP_CHECK(hipStreamSynchronize(stream()));
+    unsigned long long bad = 0;
+    memcpy(&bad, pinned, sizeof(bad));
+    if (prior_totals_out)
+        memcpy(prior_totals_out, pinned + 64, m * sizeof(float));
+    DIST_REQUIRE(bad == ~0ull,
+                 who + ": value outside its feature's domain at row "
+                     + std::to_string(bad >> 8) + ", feature "
+                     + std::to_string(bad & 0xFF));
+}
+
+void dist::Gibbs::relate_many(dist_gibbs_t * const * engines, size_t m,
+                              size_t n_samples, uint32_t seed_state,
+                              uint32_t member_seed_state, uint64_t draw_base,
+                              double * mi_out, double * stderr_out,
+                              double * moments_out, bool single) {
+    const std::string who = single ? "relate" : "relate_many";
+    const std::vector<Gibbs *> e = marginals_engines(engines, m, single, who);
+    DIST_REQUIRE(n_samples >= 1, who + ": no sample");
+    Gibbs & first = *e[0];
+    const int F = first.F();
+    DIST_REQUIRE(F >= 1, who + ": no feature");
+    // the masks: every feature alone, then the pairs (i, j), i < j, in
+    // row-major order (k_relate_moments' columns)
+    std::vector<uint32_t> masks;
+    for (int i = 0; i < F; ++i) masks.push_back(1u << i);
+    for (int i = 0; i < F; ++i)
+        for (int j = i + 1; j < F; ++j) masks.push_back(1u << i | 1u << j);
+    const size_t S = masks.size();
+    const size_t n = n_samples;
+    size_t step = std::min(n, (size_t)first.opt.predict_chunk);
+    step = std::min(step, std::max<size_t>(1, kManyScratchWords / (m * S)));
+    step = std::min(step, std::max<size_t>(1, (size_t)INT_MAX / S));
+    const uint32_t * cols_in[kMaxF] = {};
+    uint32_t * cols_out[kMaxF] = {};
+    for (int f = 0; f < F; ++f) {
+        first.relate_cols[f].reserve(step, 0);
+        cols_in[f] = cols_out[f] = first.relate_cols[f].p;
+    }
+    first.relate_l.reserve(step * S, 0);
+    const size_t cells = (size_t)F * F;
+    first.relate_acc.reserve(3 * cells, 0);
+    HIP_CHECK(hipMemsetAsync(first.relate_acc.p, 0,
+                             3 * cells * sizeof(double), stream()));
+    for (size_t c0 = 0; c0 < n; c0 += step) {
+        const size_t rows = std::min(n, c0 + step) - c0;
+        // the rows sample_rows_many(n, seed, member_seed, draw_base) gives at
+        // [c0, c0 + rows): row q depends on draw_base + q alone
+        sample_rows_many_enqueue(e, rows, nullptr, nullptr, cols_out, nullptr,
+                                 nullptr, nullptr, seed_state,
+                                 member_seed_state, draw_base + c0, c0 == 0,
+                                 c0);
+        marginals_enqueue(e, rows, cols_in, masks.data(), S, first.relate_l.p,
+                          nullptr, 0, false, single, c0 == 0, c0, who);
+        hipLaunchKernelGGL(k_relate_moments, dim3((unsigned)cells),
+                           dim3(kBlock), 0, stream(), first.relate_l.p, rows,
+                           F, c0 == 0 ? 1 : 0, first.relate_acc.p);
+        HIP_CHECK(hipGetLastError());
+    }
+    // the call's one wait: the moments and the error words
+    const size_t acc_bytes = 3 * cells * sizeof(double);
+    char * pinned = chain_pinned(64 + acc_bytes);
     HIP_CHECK(hipMemcpyAsync(pinned, first.sample_bad.p,
                              2 * sizeof(unsigned long long),
                              hipMemcpyDeviceToHost, stream()));
+    HIP_CHECK(hipMemcpyAsync(pinned + 16, first.predict_bad.p,
+                             sizeof(unsigned long long),
+                             hipMemcpyDeviceToHost, stream()));
+    HIP_CHECK(hipMemcpyAsync(pinned + 64, first.relate_acc.p, acc_bytes,
+                             hipMemcpyDeviceToHost, stream()));
     HIP_CHECK(hipStreamSynchronize(stream()));
-    unsigned long long bad[2] = {0, 0};
+    unsigned long long bad[3] = {0, 0, 0};
     memcpy(bad, pinned, sizeof(bad));
-    DIST_REQUIRE(bad[0] == ~0ull,
-                 who + ": observed value outside its feature's domain (or in "
-                       "a column that was not given) at row "
-                     + std::to_string(bad[0] >> 8) + ", feature "
-                     + std::to_string(bad[0] & 0xFF));
-    DIST_REQUIRE(bad[1] == ~0ull,
-                 who + ": a cell's bounded draw ran out of tries (NaN or "
-                       "degenerate hyper-parameters?) at row "
-                     + std::to_string(bad[1] >> 8) + ", feature "
-                     + std::to_string(bad[1] & 0xFF));
+    sample_rows_many_report(bad, who);
+    DIST_REQUIRE(bad[2] == ~0ull,
+                 who + ": drawn value outside its feature's domain at row "
+                     + std::to_string(bad[2] >> 8) + ", feature "
+                     + std::to_string(bad[2] & 0xFF));
+    std::vector<double> acc(3 * cells);
+    memcpy(acc.data(), pinned + 64, acc_bytes);
+    const double dn = (double)n;
+    for (int i = 0; i < F; ++i)
+        for (int j = i; j < F; ++j) {
+            // the sums of d - shift and of its square (k_relate_moments)
+            const double a = acc[3 * ((size_t)i * F + j)];
+            const double b = acc[3 * ((size_t)i * F + j) + 1];
+            const double shift = acc[3 * ((size_t)i * F + j) + 2];
+            const double sums[2] = {a + dn * shift,
+                                    b + shift * (2.0 * a + dn * shift)};
+            const double mean = sums[0] / dn;
+            double se = std::numeric_limits<double>::infinity();
+            if (n > 1) {
+                // (NaN moments stay NaN: the comparison is false for them)
+                double var = (b - a * (a / dn)) / (dn - 1.0);
+                if (var < 0.0) var = 0.0;
+                se = std::sqrt(var / dn);
+            }
+            if (moments_out)
+                for (int c = 0; c < 2; ++c)
+                    moments_out[2 * ((size_t)i * F + j) + c] =
+                        moments_out[2 * ((size_t)j * F + i) + c] = sums[c];
+            if (mi_out)
+                mi_out[(size_t)i * F + j] = mi_out[(size_t)j * F + i] = mean;
+            if (stderr_out)
+                stderr_out[(size_t)i * F + j] =
+                    stderr_out[(size_t)j * F + i] = se;
+        }
 }
 
 extern "C" {
@@ -8404,6 +8814,106 @@ int dist_gibbs_sample_rows_many(
         if (group_out) group.download(group_out, n_rows);
         if (member_out) member.download(member_out, n_rows);
         if (base_out) base.download(base_out, n_rows);
+    });
+}
+// the host forms of the marginals: named columns go up, the planes come back
+static void marginals_host(dist_gibbs_t * const * engines, size_t m,
+                           size_t n_rows, const uint32_t * const * values,
+                           const uint32_t * masks, size_t n_masks,
+                           float * logp_out, float * members_out,
+                           size_t members_ld, float * prior_totals_out,
+                           bool single) {
+    DIST_REQUIRE(engines && m >= 1 && engines[0],
+                 std::string(single ? "marginals" : "marginals_many")
+                     + ": no engine");
+    const int F = engines[0]->impl.read()->F();
+    std::vector<DeviceBuf<uint32_t>> cols((size_t)F);
+    std::vector<const uint32_t *> ptrs((size_t)F, nullptr);
+    for (int f = 0; f < F && n_rows && values; ++f) {
+        if (values[f] == nullptr) continue;
+        cols[f].upload(values[f], n_rows);
+        ptrs[f] = cols[f].p;
+    }
+    const size_t S = std::max<size_t>(n_masks, 1);
+    DIST_REQUIRE(!members_out || members_ld / S >= n_rows,
+                 "marginals_many: members_ld is less than rows x masks");
+    const size_t cells = std::max<size_t>(n_rows, 1) * S;
+    DeviceBuf<float> logp, planes;
+    if (logp_out) logp.reserve(cells, 0);
+    if (members_out) planes.reserve(m * cells, 0);
+    Gibbs::marginals_many(engines, m, n_rows, ptrs.data(), masks, n_masks,
+                          logp.p, planes.p, n_rows * S, prior_totals_out,
+                          single);
+    if (!n_rows) return;
+    if (logp_out) logp.download(logp_out, n_rows * S);
+    if (members_out) {
+        HIP_CHECK(hipMemcpy2DAsync(
+            members_out, members_ld * sizeof(float), planes.p,
+            n_rows * S * sizeof(float), n_rows * S * sizeof(float), m,
+            hipMemcpyDeviceToHost, stream()));
+        dist::sync();
+    }
+}
+int dist_gibbs_marginals_dev(dist_gibbs_t * g, size_t n_rows,
+                             const uint32_t * const * values_dev,
+                             const uint32_t * masks, size_t n_masks,
+                             float * logp_dev) {
+    return guarded([&] {
+        dist_gibbs_t * one[1] = {g};
+        Gibbs::marginals_many(one, 1, n_rows, values_dev, masks, n_masks,
+                              logp_dev, nullptr, 0, nullptr, true);
+    });
+}
+int dist_gibbs_marginals(dist_gibbs_t * g, size_t n_rows,
+                         const uint32_t * const * values,
+                         const uint32_t * masks, size_t n_masks,
+                         float * logp_out) {
+    return guarded([&] {
+        dist_gibbs_t * one[1] = {g};
+        marginals_host(one, 1, n_rows, values, masks, n_masks, logp_out,
+                       nullptr, 0, nullptr, true);
+    });
+}
+int dist_gibbs_marginals_many_dev(
+        dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+        const uint32_t * const * values_dev, const uint32_t * masks,
+        size_t n_masks, float * logp_dev, float * members_logp_dev,
+        size_t members_ld, float * prior_totals_out) {
+    return guarded([&] {
+        Gibbs::marginals_many(engines, m, n_rows, values_dev, masks, n_masks,
+                              logp_dev, members_logp_dev, members_ld,
+                              prior_totals_out, false);
+    });
+}
+int dist_gibbs_marginals_many(
+        dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+        const uint32_t * const * values, const uint32_t * masks,
+        size_t n_masks, float * logp_out, float * members_logp_out,
+        size_t members_ld, float * prior_totals_out) {
+    return guarded([&] {
+        marginals_host(engines, m, n_rows, values, masks, n_masks, logp_out,
+                       members_logp_out, members_ld, prior_totals_out, false);
+    });
+}
+int dist_gibbs_relate(dist_gibbs_t * g, size_t n_samples, uint32_t seed_state,
+                      uint32_t member_seed_state, uint64_t draw_base,
+                      double * mi_out, double * stderr_out,
+                      double * moments_out) {
+    return guarded([&] {
+        dist_gibbs_t * one[1] = {g};
+        Gibbs::relate_many(one, 1, n_samples, seed_state, member_seed_state,
+                           draw_base, mi_out, stderr_out, moments_out, true);
+    });
+}
+int dist_gibbs_relate_many(dist_gibbs_t * const * engines, size_t m,
+                           size_t n_samples, uint32_t seed_state,
+                           uint32_t member_seed_state, uint64_t draw_base,
+                           double * mi_out, double * stderr_out,
+                           double * moments_out) {
+    return guarded([&] {
+        Gibbs::relate_many(engines, m, n_samples, seed_state,
+                           member_seed_state, draw_base, mi_out, stderr_out,
+                           moments_out, false);
     });
 }
 size_t dist_gibbs_group_count(const dist_gibbs_t * g) {

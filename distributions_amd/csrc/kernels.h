@@ -30,6 +30,7 @@ constexpr size_t kLdsWorkgroupLimit = 144 * 1024;
 #include "kernels_coassign.h"
 #include "kernels_coassign_topk.h"
 #include "kernels_feature.h"
+#include "kernels_marginals.h"
 #include "kernels_sample.h"
 #include "kernels_sample_many.h"
 #include "kernels_vs.h"

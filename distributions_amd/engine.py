@@ -283,6 +283,33 @@ class Gibbs(object):
             0 if staged else _core.PREDICT_FEATURE_RECOMPUTE)
         return joint, base, choice
 
+    def marginals(self, values, masks):
+        """marginals_many on this engine alone (dist_gibbs_marginals)
+        -> logp float32 [n, S]: no fold and no - log M.  logp[q, s] is
+        `predict_feature(values, target=t, observed=[masks[s]] * n,
+        mode=None)`'s base for any t outside masks[s], for the mask of all
+        features `predict`'s logp, for mask 0 its prior_total -- bit for bit
+        under PitmanYor; under LowEntropy each minus prior_total (one float
+        subtraction), which makes it a proper log density."""
+        return _core.marginals_many([self.core], list(values), masks, False,
+                                    True)[0]
+
+    def marginals_torch(self, values, masks):
+        """marginals for device tensors -> a [n, S] tensor"""
+        return _marginals_torch([self], values, masks, False, True)[0]
+
+    def relate(self, n_samples, seed=0, member_seed=None, draw_base=0,
+               moments=False):
+        """relate_many on this engine alone (dist_gibbs_relate): the rows are
+        `sample_rows_many([self], n_samples, ...)`'s, which are
+        `sample_rows`', scored by `marginals` (no fold).
+        -> (mi [F, F] float64, stderr [F, F] float64)"""
+        if member_seed is None:
+            member_seed = seed + 1
+        out = _core.relate_many([self.core], n_samples, _core.rng_seed(seed),
+                                _core.rng_seed(member_seed), draw_base, True)
+        return out if moments else out[:2]
+
     def sample_rows(self, n=None, values=None, observed=None, seed=0,
                     draw_base=0):
         """Rows that are NOT in the table, drawn from the mixture: synthetic
@@ -689,6 +716,104 @@ def predict_feature_many_torch(engines, values, target, candidates=None,
         int(pj.data_ptr()) if pj is not None else 0, n * C,
         int(pb.data_ptr()) if pb is not None else 0, n, True)
     return joint, base, choice, chosen, pj, pb, totals
+
+
+def marginals_many(engines, values, masks, members=False):
+    """Rows that are NOT in the table: the log marginals of S feature subsets
+    per row, averaged over the members of an ensemble of M engines (the
+    chains of sweep_sequential_many, each one posterior sample).
+    values: one host array per feature; None for a feature no mask names
+    (words of such features are never read).  masks: S >= 1 uint32 shared by
+    all rows, bit f set when the subset names feature f; duplicates and 0 are
+    allowed; a bit beyond the feature list, or a named feature whose column is
+    None, fails before any launch naming the mask's index.
+    -> (logp [n, S] float32, members_logp [M, n, S] or None, prior_totals
+    [M]):
+    members_logp[e, q, s] = log_sum_exp over all groups of engine e, empty
+    ones included, of the clustering model's score_value folded in feature
+    order with the score_value of every feature in masks[s] at row q's value
+    (mixture.hpp:416-425, random.cc:78-92); an unnamed feature contributes
+    nothing; under LowEntropy minus that engine's prior_total.  It is
+    `Gibbs.predict_feature`'s base under the row mask masks[s] (any target
+    outside it), `predict`'s logp for the mask of all features and its
+    prior_total for mask 0, bit for bit.
+    logp[q, s] = log (1/M) sum_e p(x_q[masks[s]] | engine e): the in-order
+    log_sum_exp over the engines minus fast_log(M), as `predict_many` and
+    `predict_feature_many` fold theirs.  Every feature's term is evaluated
+    once per (engine, row, group) and shared by the S subsets.  A named
+    DirichletDiscrete value >= dim or BetaBernoulli value > 1 fails naming the
+    first such row.  The engines share one feature list and one clustering
+    model; nothing in them changes."""
+    return _core.marginals_many(_cores(engines), list(values), masks, members)
+
+
+def _marginals_torch(engines, values, masks, members, single):
+    import torch
+    given = [v for v in values if v is not None]
+    if not given:
+        raise RuntimeError("marginals_many: no column tells the number of "
+                           "rows")
+    # (contiguous, 4 bytes per row, one length, one CUDA device)
+    checked = iter(_device_columns(given))
+    values = [None if v is None else next(checked) for v in values]
+    given = [v for v in values if v is not None]
+    n = int(given[0].numel())
+    dev = given[0].device
+    masks = np.ascontiguousarray(masks, dtype=np.uint32).reshape(-1)
+    S = max(len(masks), 1)
+    logp = torch.empty((n, S), dtype=torch.float32, device=dev)
+    planes = None
+    if members:
+        planes = torch.empty((len(engines), n, S), dtype=torch.float32,
+                             device=dev)
+    # (the library works on its own stream: what filled the tensors on
+    # torch's must be done)
+    torch.cuda.current_stream(dev).synchronize()
+    totals = _core.marginals_many_dev(
+        _cores(engines),
+        [0 if v is None else int(v.data_ptr()) for v in values], n, masks,
+        int(logp.data_ptr()),
+        int(planes.data_ptr()) if planes is not None else 0, n * S, True,
+        single)
+    return logp, planes, totals
+
+
+def marginals_many_torch(engines, values, masks, members=False):
+    """marginals_many for device tensors (one 4-byte-per-row CUDA tensor per
+    feature, None for a feature no mask names; masks stay a host list): logp
+    and members_logp are tensors on the same device and nothing is staged
+    through the host; prior_totals is numpy.
+    -> (logp, members_logp, prior_totals)"""
+    return _marginals_torch(engines, values, masks, members, False)
+
+
+def relate_many(engines, n_samples, seed=0, member_seed=None, draw_base=0,
+                moments=False):
+    """Which columns depend on each other: the mutual information of every
+    feature pair, and every feature's entropy, under the ensemble's predictive
+    p = (1/M) sum_e p_e, estimated from n_samples rows drawn from it.
+    -> (mi [F, F] float64, stderr [F, F] float64).
+    The rows are the ones `sample_rows_many(engines, n_samples, seed=seed,
+    member_seed=member_seed, draw_base=draw_base)` returns (nothing observed);
+    they are scored on the device by `marginals_many` with the masks {i} and
+    {i, j}, and mi[i, j] = mi[j, i] is the mean over the rows of
+    d = logp_ij - logp_i - logp_j, mi[i, i] the mean of -logp_i: the entropy
+    of feature i (the differential entropy of a NormalInverseChiSq feature;
+    under LowEntropy the members are normalised, so it is that of a proper
+    density).  stderr = sqrt(sample variance of d / n_samples), +inf for one
+    row; none fails.  The moments are summed in float64 in a fixed order:
+    equal calls give equal bits.  A Monte Carlo estimate of a pair's mutual
+    information can be slightly negative.  A drawn row whose marginals are not
+    finite makes the cells it enters NaN.  Conditional variants are composed
+    from `sample_rows_many(values, observed)` and `marginals_many`.
+    moments=True adds the sums themselves, [F, F, 2] float64 (sum d, sum
+    d^2), which pool over calls of disjoint draw_base ranges.  Nothing in the
+    engines changes."""
+    if member_seed is None:
+        member_seed = seed + 1
+    out = _core.relate_many(_cores(engines), n_samples, _core.rng_seed(seed),
+                            _core.rng_seed(member_seed), draw_base)
+    return out if moments else out[:2]
 
 
 def sample_rows_many(engines, n=None, values=None, observed=None, seed=0,

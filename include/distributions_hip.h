@@ -1040,6 +1040,112 @@ int dist_gibbs_sample_rows_many(
     float * base_out, uint32_t seed_state, uint32_t member_seed_state,
     uint64_t draw_base, unsigned flags);
 
+/* Held-out rows: the log marginals of S feature subsets per row, on one
+ * engine and averaged over the members of an ensemble of m engines
+ * (dist_gibbs_predict_many's ensembles).  An extension: the reference has no
+ * such member, only the folds reused here.  masks: a HOST array of n_masks
+ * >= 1 words shared by all rows, bit f of masks[s] set when subset s names
+ * feature f; duplicates and 0 are allowed.  For query row q, subset s and
+ * engine e in [0, m):
+ *   scores[k], k in [0, dist_gibbs_group_count), empty groups included: the
+ *     driver's score_value as in dist_gibbs_predict, then in feature order
+ *     (mixture.hpp:416-425) the score_value of every feature NAMED by masks[s]
+ *     with the row's value; an unnamed feature contributes nothing --
+ *     dist_gibbs_predict_feature's `base` fold with the mask per subset
+ *     instead of per row;
+ *   w[e][q * n_masks + s] = log_sum_exp(scores) (random.cc:78-92); under
+ *     LowEntropy minus that engine's prior_total, one float subtraction (under
+ *     PitmanYor nothing is subtracted).  For any target outside masks[s] it is
+ *     dist_gibbs_predict_feature's base under the row mask masks[s], bit for
+ *     bit (minus prior_total under LowEntropy); for the mask of all features
+ *     dist_gibbs_predict's logp, for mask 0 its prior_total (under LowEntropy
+ *     x - x);
+ *   dist_gibbs_marginals: logp[q * n_masks + s] = w[0][q * n_masks + s], one
+ *     engine and no fold;
+ *   dist_gibbs_marginals_many: logp[q * n_masks + s] =
+ *     log_sum_exp(w[0..m)[q * n_masks + s]) - fast_log((float)m), with
+ *     log_sum_exp as random.cc:78-92 has it -- the maximum, the in-order float
+ *     sum of fast_exp(w - max), fast_log(total) + max: the log of
+ *     (1/m) sum_e p(x_S | e), as dist_gibbs_predict_feature_many folds base;
+ *   members_logp: the planes w, plane e at members_logp + e * members_ld
+ *     (members_ld >= n_rows * n_masks); prior_totals_out[e]: engine e's
+ *     prior_total, a HOST array of m floats.
+ * logp, members_logp and prior_totals_out may be NULL.
+ * values: F columns of n_rows words; a column may be NULL for a feature no
+ * mask names, and words of such features are never read.  A mask with a bit
+ * >= F, or one that names a feature whose column is NULL, fails before any
+ * launch naming the mask's index.  A DirichletDiscrete value >= dim or a
+ * BetaBernoulli value > 1 under a NAMED feature fails the call naming the
+ * first such row and its feature; a DirichletProcessDiscrete value the table
+ * does not hold scores as OTHER.  The engines are distinct and share one
+ * feature list (kinds and dim) and one clustering model, at most 65535 of
+ * them.  A pure reader of every engine under dist_gibbs_predict_many's rules:
+ * a run a sweep left open stays resumable, an open batch or stale cells on
+ * any engine are refused.  Scratch: m x chunk x n_masks floats for w unless
+ * members_logp is given; chunk keeps them under 1 GiB and is at most the
+ * first engine's "debug.predict_chunk"; results do not depend on it or on
+ * launch geometry.  One host wait per call.
+ * _dev: device pointers throughout; engines, values_dev (F device pointers),
+ * masks and prior_totals_out are host arrays.  The host form stages, calls
+ * and downloads. */
+int dist_gibbs_marginals_dev(dist_gibbs_t * g, size_t n_rows,
+                             const uint32_t * const * values_dev,
+                             const uint32_t * masks, size_t n_masks,
+                             float * logp_dev);
+int dist_gibbs_marginals(dist_gibbs_t * g, size_t n_rows,
+                         const uint32_t * const * values,
+                         const uint32_t * masks, size_t n_masks,
+                         float * logp_out);
+int dist_gibbs_marginals_many_dev(
+    dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+    const uint32_t * const * values_dev, const uint32_t * masks,
+    size_t n_masks, float * logp_dev, float * members_logp_dev,
+    size_t members_ld, float * prior_totals_out);
+int dist_gibbs_marginals_many(
+    dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+    const uint32_t * const * values, const uint32_t * masks, size_t n_masks,
+    float * logp_out, float * members_logp_out, size_t members_ld,
+    float * prior_totals_out);
+
+/* Which columns depend on each other: the mutual information of every feature
+ * pair and the entropy of every feature under the predictive of one engine or
+ * of an ensemble of m engines, estimated from n_samples rows drawn from it.
+ * An extension: the reference has no such member.  Per chunk of rows, on the
+ * device:
+ *   the rows are those dist_gibbs_sample_rows_many draws with nothing
+ *     observed for the same seed_state, member_seed_state and draw_base;
+ *   L = dist_gibbs_marginals_many's logp of them (dist_gibbs_relate:
+ *     dist_gibbs_marginals', one engine and no fold) under the masks {i}
+ *     (i < F) and {i, j} (i < j);
+ *   per pair, in double, with
+ *     d_q = (double)L_ij[q] - (double)L_i[q] - (double)L_j[q] and c the d of
+ *     the call's first row: sum_q (d_q - c) and sum_q (d_q - c)^2 -- shifted,
+ *     so that the variance does not cancel where |mean| is many standard
+ *     deviations; per feature the same of -(double)L_i[q].  sum d and sum d^2
+ *     are formed from them on the host.  No floating-point atomics: a fixed
+ *     tree per chunk and an in-order add over the chunks, so equal calls give
+ *     equal bits.
+ * mi_out[i * F + j] = mi_out[j * F + i] = the mean of d; mi_out[i * F + i] the
+ * entropy estimate of feature i (the differential entropy of a
+ * NormalInverseChiSq feature); stderr_out the square root of (sample variance
+ * / n_samples), +inf for n_samples == 1.  Both are HOST arrays of F * F
+ * doubles and may be NULL; moments_out, a HOST array of F * F * 2 doubles or
+ * NULL, takes the sums themselves, cell (i, j) at [(i * F + j) * 2]: sum d,
+ * then sum d^2 (what a caller pools over calls of disjoint draw_base ranges).
+ * n_samples == 0 fails.  A drawn row whose L is not
+ * finite makes the cells it enters NaN.  Conditional variants are composed by
+ * the caller from dist_gibbs_sample_rows_many and dist_gibbs_marginals_many.
+ * The engines: dist_gibbs_marginals_many's rules.  One host wait per call. */
+int dist_gibbs_relate(dist_gibbs_t * g, size_t n_samples, uint32_t seed_state,
+                      uint32_t member_seed_state, uint64_t draw_base,
+                      double * mi_out, double * stderr_out,
+                      double * moments_out);
+int dist_gibbs_relate_many(dist_gibbs_t * const * engines, size_t m,
+                           size_t n_samples, uint32_t seed_state,
+                           uint32_t member_seed_state, uint64_t draw_base,
+                           double * mi_out, double * stderr_out,
+                           double * moments_out);
+
 size_t dist_gibbs_group_count(const dist_gibbs_t * g);     /* counts().size() */
 size_t dist_gibbs_row_count(const dist_gibbs_t * g);
 int dist_gibbs_counts(const dist_gibbs_t * g, int * out);  /* driver counts() */
