@@ -380,6 +380,13 @@ cdef extern from "distributions_hip.h" nogil:
     int dist_gibbs_sample_clustering(dist_gibbs_t *, const float *,
                                      const float *, size_t, uint32_t *,
                                      size_t *)
+    int dist_gibbs_sample_hypers_pass(dist_gibbs_t *, int, const int *,
+                                      size_t, const float *, size_t, size_t,
+                                      uint32_t *, uint32_t *)
+    int dist_gibbs_sample_hypers_pass_many(dist_gibbs_t * const *, size_t,
+                                           int, const int *, size_t,
+                                           const float *, size_t, size_t,
+                                           uint32_t *, uint32_t *)
     int dist_gibbs_hyper_stats(dist_gibbs_t *, uint64_t *)
 
 
@@ -1961,11 +1968,84 @@ cdef class GibbsEngine:
             a.shape[0], &rng_state, &chosen))
         return chosen, rng_state
 
+    def sample_hypers_pass(self, int feature, grids, uint32_t rng_state,
+                           coords=None):
+        """a whole coordinate pass of a DirichletDiscrete feature
+        (dist_gibbs_sample_hypers_pass): grids float32 [n_coords, G] or one
+        row [G] for every step, coords default 0 .. dim-1
+        -> (indices uint32 [n_coords], new rng state)"""
+        cdef cnp.ndarray[cnp.int32_t, ndim=1] co
+        cdef cnp.ndarray[cnp.float32_t, ndim=2] gr
+        cdef size_t stride
+        co, gr, stride = _pass_arguments(self, feature, grids, coords)
+        cdef size_t n = co.shape[0], G = gr.shape[1]
+        cdef cnp.ndarray[cnp.uint32_t, ndim=1] chosen = np.zeros(n, np.uint32)
+        cdef int rc
+        with nogil:
+            rc = dist_gibbs_sample_hypers_pass(
+                self.ptr, feature, <const int *> co.data, n,
+                <const float *> gr.data, G, stride, &rng_state,
+                <uint32_t *> chosen.data)
+        check(rc)
+        self.shareds[feature] = self.shared(feature)
+        return chosen, rng_state
+
     def hyper_stats(self):
         """-> (accumulator chains, candidates scored, launches, calls)"""
         cdef uint64_t out[4]
         check(dist_gibbs_hyper_stats(self.ptr, out))
         return out[0], out[1], out[2], out[3]
+
+
+def _pass_arguments(GibbsEngine first, int feature, grids, coords):
+    """-> (coords int32 [n], grid float32 [n or 1, G], grid_stride)"""
+    gr = np.ascontiguousarray(grids, dtype=np.float32)
+    if gr.ndim not in (1, 2):
+        raise ValueError("grids: [n_coords, G], or [G] for every step")
+    if coords is None:
+        coords = np.arange(first.shared(feature).dim)
+    co = np.ascontiguousarray(coords, dtype=np.int32).ravel()
+    if gr.ndim == 2 and gr.shape[0] != co.shape[0]:
+        raise ValueError("one grid per coordinate step")
+    stride = gr.shape[1] if gr.ndim == 2 else 0
+    # (no negative index: the module is compiled with wraparound=False)
+    if gr.ndim == 1:
+        gr = gr.reshape(1, gr.shape[0])
+    return co, gr, stride
+
+
+def sample_hypers_pass_many(engines, int feature, grids, rng_states,
+                            coords=None):
+    """the pass on M engines in the same launches
+    (dist_gibbs_sample_hypers_pass_many): engines = GibbsEngine objects
+    -> (indices uint32 [M, n_coords], new states uint32 [M])"""
+    cdef size_t m = len(engines)
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] st = np.ascontiguousarray(
+        rng_states, dtype=np.uint32).copy()
+    if <size_t> st.shape[0] != m:
+        raise ValueError("one rng state per engine")
+    cdef cnp.ndarray[cnp.int32_t, ndim=1] co
+    cdef cnp.ndarray[cnp.float32_t, ndim=2] gr
+    cdef size_t stride
+    if not m:
+        return np.zeros((0, 0), np.uint32), st
+    co, gr, stride = _pass_arguments(engines[0], feature, grids, coords)
+    cdef size_t n = co.shape[0], G = gr.shape[1]
+    cdef cnp.ndarray[cnp.uint32_t, ndim=2] chosen = np.zeros((m, n),
+                                                             np.uint32)
+    cdef dist_gibbs_t ** ptrs = _engine_ptrs(engines)
+    cdef int rc
+    with nogil:
+        rc = dist_gibbs_sample_hypers_pass_many(
+            <dist_gibbs_t * const *> ptrs, m, feature,
+            <const int *> co.data, n, <const float *> gr.data, G, stride,
+            <uint32_t *> st.data, <uint32_t *> chosen.data)
+    free(ptrs)
+    check(rc)
+    cdef GibbsEngine e
+    for e in engines:
+        e.shareds[feature] = e.shared(feature)
+    return chosen, st
 
 
 def sweep_sequential_many(engines, size_t row_begin, size_t row_end,

@@ -245,6 +245,17 @@ static void release_small_lgamma(const std::vector<float> & ys) {
             it->second.users -= 1;
     }
 }
+// whether the device's table holds every argument below 2.5 among `ys` (a
+// full table drops what does not fit without a word)
+static bool small_lgamma_registered(const std::vector<float> & ys) {
+    std::lock_guard<std::mutex> lock(g_init_mutex);
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    const std::map<float, LgammaEntry> & table = g_lgamma_registered[dev];
+    for (float y : ys)
+        if (y > 0.f && y < 2.5f && !table.count(y)) return false;
+    return true;
+}
 
 // the arguments below 2.5 that MixtureDataScorer::score_data hands to
 // fast_lgamma for groups of at most two members under `sh` (dd.hpp:287-318,
@@ -2179,6 +2190,228 @@ struct Gibbs {
         rebuild_caches();
         sync();
         *chosen = pick;
+    }
+
+    // ---- a whole coordinate pass of a DirichletDiscrete feature
+    // (dist_gibbs_sample_hypers_pass[_many]; kernels_hyper.h).
+    // The engines arrive settled.  Everything is checked before anything is
+    // launched or installed; then every engine whose pass the device can
+    // reproduce exactly goes through the same two launches, and the others
+    // through the loop of sample_hypers calls that defines the result.
+    static constexpr double kPassMinAlphaSum = 3.0;   // see pass_on_device
+    static constexpr double kPassMaxAlphaSum = 1.0e9;
+    static constexpr size_t kPassMaxCandidates = (size_t)1 << 24;
+    static constexpr int kHyperPassLaunches = 2;
+
+    // The loop's arithmetic needs the host where fast_lgamma of an alpha_sum
+    // leaves its polynomial: below 2.5 it is glibc's lgammaf per registered
+    // argument, and which sums occur depends on the draws.  least / most: per
+    // coordinate the smallest / largest value it can hold during the pass.
+    // Every alpha_sum the pass forms is a float sum of dim <= 256 positive
+    // terms (or that sum carried in binary64 and rounded once), within
+    // 256 * 2^-24 < 2e-5 relative of the exact sum, which is >= the binary64
+    // sum of `least`: from 3.0 up the float is above 2.99, clear of 2.5.
+    // At the other end alpha_sum + a group's size (< 2^31) must stay below
+    // fast_lgamma's 2^32 branch: sums up to 1e9 do.
+    bool pass_on_device(const Slave & s, const std::vector<float> & least,
+                        const std::vector<float> & most, size_t n_coords,
+                        size_t G) const {
+        bool members = false;
+        for (int c : py.counts) members = members || c > 0;
+        if (!members || !s.K) return false;   // (K == 0 included)
+        if (G > (size_t)kHyperPassMaxGrid) return false;
+        if (n_coords * G > kPassMaxCandidates) return false;
+        double lo = 0.0, hi = 0.0;
+        for (int u = 0; u < s.sh.dim; ++u) {
+            lo += (double)std::min(s.sh.alphas[u], least[(size_t)u]);
+            hi += (double)std::max(s.sh.alphas[u], most[(size_t)u]);
+        }
+        return lo >= kPassMinAlphaSum && hi <= kPassMaxAlphaSum;
+    }
+    // today's loop, which defines the result
+    void pass_by_loop(int f, const int * coords, size_t n_coords,
+                      const float * grid, size_t G, size_t stride,
+                      uint32_t * rng_state, uint32_t * chosen) {
+        std::vector<dist_shared_t> cands(G);
+        for (size_t i = 0; i < n_coords; ++i) {
+            const float * g = grid + i * stride;
+            for (size_t c = 0; c < G; ++c) {
+                cands[c] = feats[(size_t)f]->sh;
+                cands[c].alphas[coords[i]] = g[c];
+            }
+            size_t pick = 0;
+            sample_hypers(f, cands.data(), G, rng_state, &pick);
+            chosen[i] = (uint32_t)pick;
+        }
+    }
+    static void sample_hypers_pass_many(
+            const std::vector<Gibbs *> & e, int f, const int * coords,
+            size_t n_coords, const float * grid, size_t G, size_t stride,
+            uint32_t * rng_states, uint32_t * chosen) {
+        static const char * const kinds[] = {
+            "DirichletDiscrete", "BetaBernoulli", "GammaPoisson",
+            "NormalInverseChiSq", "DirichletProcessDiscrete",
+            "BetaNegativeBinomial"};
+        const std::string who = "sample_hypers_pass";
+        const size_t m = e.size();
+        if (!m) return;
+        DIST_REQUIRE(m <= 65535, who + ": at most 65535 engines");
+        for (Gibbs * g : e) {
+            DIST_REQUIRE(!g->batch_open, who + ": a batch is open");
+            g->ex.require_whole(who.c_str());
+            const Slave & s = g->hyper_feature(f, who.c_str());
+            DIST_REQUIRE(s.sh.kind == DIST_DD,
+                         who + ": built for DirichletDiscrete, feature "
+                             + std::to_string(f) + " is "
+                             + kinds[s.sh.kind]);
+            DIST_REQUIRE(s.sh.dim == e[0]->feats[(size_t)f]->sh.dim,
+                         who + ": the feature has one dim across engines");
+        }
+        const int dim = e[0]->feats[(size_t)f]->sh.dim;
+        DIST_REQUIRE(G >= 1, who + ": expected 0 < grid_size");
+        DIST_REQUIRE(G <= 0x7FFFFFFFu, who + ": too many candidates");
+        DIST_REQUIRE(stride == 0 || stride >= G,
+                     who + ": grid_stride is 0 or at least grid_size");
+        DIST_REQUIRE(n_coords == 0 || (coords && grid), "null argument");
+        std::vector<float> least((size_t)dim, INFINITY),
+            most((size_t)dim, 0.f);
+        for (size_t i = 0; i < n_coords; ++i) {
+            DIST_REQUIRE(coords[i] >= 0 && coords[i] < dim,
+                         who + ": coordinate out of bounds: "
+                             + std::to_string(coords[i]));
+            const float * g = grid + i * stride;
+            for (size_t c = 0; c < G; ++c) {
+                DIST_REQUIRE(g[c] > 0.f && g[c] < INFINITY,
+                             who + ": expected a finite grid value > 0, "
+                                   "got " + std::to_string(g[c]));
+                float & lo = least[(size_t)coords[i]];
+                float & hi = most[(size_t)coords[i]];
+                lo = std::min(lo, g[c]);
+                hi = std::max(hi, g[c]);
+            }
+        }
+        if (!n_coords) return;
+
+        auto bits = [](float x) { uint32_t u; memcpy(&u, &x, 4); return u; };
+        std::vector<size_t> dev;
+        for (size_t j = 0; j < m; ++j)
+            if (e[j]->pass_on_device(*e[j]->feats[(size_t)f], least, most,
+                                     n_coords, G))
+                dev.push_back(j);
+        // the grid's chains, one per distinct (coordinate, value) by bits,
+        // and the arguments below 2.5 they reach (value + 0, 1, 2: groups of
+        // at most two members, dd.hpp:287-318), held for the call
+        std::vector<HyperJob> jobs;
+        std::vector<int> grid_job;
+        std::vector<float> grid_args;
+        if (!dev.empty()) {
+            std::map<std::pair<int, uint32_t>, int> met;
+            std::set<uint32_t> small;
+            grid_job.resize(n_coords * G);
+            for (size_t i = 0; i < n_coords; ++i)
+                for (size_t c = 0; c < G; ++c) {
+                    const float a = grid[i * stride + c];
+                    auto at = met.emplace(std::make_pair(coords[i], bits(a)),
+                                          (int)jobs.size());
+                    if (at.second) {
+                        jobs.push_back(HyperJob{a, coords[i]});
+                        for (int n = 0; n <= 2; ++n) {
+                            const float y = a + (float)n;
+                            if (y < 2.5f && small.insert(bits(y)).second)
+                                grid_args.push_back(y);
+                        }
+                    }
+                    grid_job[i * G + c] = dim + at.first->second;
+                }
+            // the process-wide table must hold them all at once
+            if (grid_args.size() > (size_t)kLgammaLutCap) dev.clear();
+        }
+        struct Release {
+            std::vector<float> ys;
+            ~Release() { release_small_lgamma(ys); }
+        } held;
+        if (!dev.empty()) {
+            register_small_lgamma(grid_args, true);
+            held.ys = grid_args;
+            if (!small_lgamma_registered(grid_args)) dev.clear();
+        }
+        if (!dev.empty()) {
+            const size_t nd = dev.size(), nj = jobs.size();
+            const size_t per_vals = (size_t)dim + nj, per_out = n_coords + 1;
+            DeviceBuf<float> vals, dgrid;
+            DeviceBuf<uint32_t> out;
+            DeviceBuf<HyperPassEngine> dengines;
+            DeviceBuf<HyperJob> djobs;
+            DeviceBuf<int> dcoords, dgrid_job;
+            vals.reserve(nd * per_vals, 0);
+            out.reserve(nd * per_out, 0);
+            std::vector<uint32_t> got(nd * per_out, ~0u);
+            out.upload(got.data(), got.size());
+            std::vector<HyperPassEngine> views(nd);
+            int K_max = 0;
+            for (size_t j = 0; j < nd; ++j) {
+                const Slave & s = *e[dev[j]]->feats[(size_t)f];
+                HyperPassEngine & v = views[j];
+                v.K = s.K;
+                v.dim = dim;
+                v.i0 = s.i0.p;
+                v.cnt = s.cnt.p;
+                v.alphas = s.prior.p;
+                v.vals = vals.p + j * per_vals;
+                v.out = out.p + j * per_out;
+                v.rng_state = rng_states[dev[j]];
+                K_max = std::max(K_max, s.K);
+            }
+            dengines.upload(views.data(), nd);
+            djobs.upload(jobs.data(), nj);
+            dcoords.upload(coords, n_coords);
+            dgrid.upload(grid, stride ? (n_coords - 1) * stride + G : G);
+            dgrid_job.upload(grid_job.data(), grid_job.size());
+            hipLaunchKernelGGL(k_hyper_dd_chains_many,
+                               dim3((unsigned)((per_vals + 63) / 64),
+                                    (unsigned)nd),
+                               dim3(64), 0, stream(), dengines.p, djobs.p,
+                               (int)nj);
+            HIP_CHECK(hipGetLastError());
+            const int chunk = std::max(
+                1, std::min(K_max, kHyperPassTerms / (int)G));
+            launch_lds<k_hyper_dd_pass>(
+                dim3((unsigned)nd), dim3(kHyperPassBlock),
+                k_hyper_dd_pass_lds((int)G, chunk), dengines.p, dcoords.p,
+                (int)n_coords, dgrid.p, (int)G, (int)stride, dgrid_job.p,
+                chunk);
+            out.download(got.data(), got.size());   // the one wait
+            for (size_t j = 0; j < nd; ++j)
+                for (size_t i = 0; i < n_coords; ++i)
+                    DIST_REQUIRE(got[j * per_out + i] < G,
+                                 "internal: the draw did not land");
+            // install once per engine: set_shared of the final alphas, then
+            // the caches over the groups, as sample_hypers does per step
+            for (size_t j = 0; j < nd; ++j) {
+                Gibbs & g = *e[dev[j]];
+                Slave & s = *g.feats[(size_t)f];
+                dist_shared_t last = s.sh;
+                for (size_t i = 0; i < n_coords; ++i) {
+                    chosen[dev[j] * n_coords + i] = got[j * per_out + i];
+                    last.alphas[coords[i]] =
+                        grid[i * stride + got[j * per_out + i]];
+                }
+                rng_states[dev[j]] = got[j * per_out + n_coords];
+                s.set_shared(last);
+                g.rebuild_caches();
+                g.hyper_calls += 1;
+                g.hyper_work.candidates += n_coords * G;
+                g.hyper_work.chains += per_vals + n_coords * G;
+                g.hyper_work.launches += kHyperPassLaunches;
+            }
+            sync();
+        }
+        std::vector<bool> done(m, false);
+        for (size_t j : dev) done[j] = true;
+        for (size_t j = 0; j < m; ++j)
+            if (!done[j])
+                e[j]->pass_by_loop(f, coords, n_coords, grid, G, stride,
+                                   &rng_states[j], chosen + j * n_coords);
     }
 
     // The group sizes are final once a batch's integer statistics are applied;
@@ -9024,6 +9257,45 @@ int dist_gibbs_sample_clustering(dist_gibbs_t * g, const float * alphas,
     return guarded([&] {
         DIST_REQUIRE(alphas && ds && rng_state && chosen, "null argument");
         g->impl->sample_clustering(alphas, ds, n, rng_state, chosen);
+    });
+}
+int dist_gibbs_sample_hypers_pass(dist_gibbs_t * g, int feature,
+                                  const int * coords, size_t n_coords,
+                                  const float * grid, size_t grid_size,
+                                  size_t grid_stride, uint32_t * rng_state,
+                                  uint32_t * chosen) {
+    return guarded([&] {
+        DIST_REQUIRE(g && rng_state && (chosen || !n_coords),
+                     "null argument");
+        std::vector<Gibbs *> e{&*g->impl};
+        Gibbs::sample_hypers_pass_many(e, feature, coords, n_coords, grid,
+                                       grid_size, grid_stride, rng_state,
+                                       chosen);
+    });
+}
+int dist_gibbs_sample_hypers_pass_many(dist_gibbs_t * const * engines,
+                                       size_t m, int feature,
+                                       const int * coords, size_t n_coords,
+                                       const float * grid, size_t grid_size,
+                                       size_t grid_stride,
+                                       uint32_t * rng_states,
+                                       uint32_t * chosen) {
+    return guarded([&] {
+        DIST_REQUIRE(m == 0 || (engines && rng_states
+                                && (chosen || !n_coords)),
+                     "null argument");
+        for (size_t i = 0; i < m; ++i) {
+            DIST_REQUIRE(engines[i], "null engine");
+            for (size_t j = 0; j < i; ++j)
+                DIST_REQUIRE(engines[j] != engines[i],
+                             "the same engine twice");
+        }
+        std::vector<Gibbs *> e(m);
+        for (size_t i = 0; i < m; ++i)
+            e[i] = &*engines[i]->impl;   // (settles, forgets a sharded run)
+        Gibbs::sample_hypers_pass_many(e, feature, coords, n_coords, grid,
+                                       grid_size, grid_stride, rng_states,
+                                       chosen);
     });
 }
 int dist_gibbs_hyper_stats(dist_gibbs_t * g, uint64_t out[4]) {

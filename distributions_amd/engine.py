@@ -405,6 +405,20 @@ class Gibbs(object):
         self.shareds[feature] = shareds[index]
         return index, rng_state
 
+    def sample_hypers_pass(self, feature, grids, rng_state, coords=None):
+        """A whole coordinate pass of a DirichletDiscrete feature in one
+        call: for step i, alphas[coords[i]] is given each value of grids[i]
+        (float32 [n_coords, G], or one row [G] for every step), one is drawn
+        with one engine step and takes its place before the next step.
+        coords: any order, repeats allowed; default 0 .. dim-1.  Bit for bit
+        the loop of sample_hypers calls over coordinate grids, in two launches
+        and one install where the device can reproduce it (hyper_stats tells).
+        -> (indices uint32 [n_coords], new rng state)"""
+        indices, rng_state = self.core.sample_hypers_pass(feature, grids,
+                                                          rng_state, coords)
+        self.shareds[feature] = self.core.shared(feature)
+        return indices, rng_state
+
     def sample_clustering(self, alphas, ds, rng_state):
         """-> (index, new rng state); (alphas[index], ds[index]) installed"""
         index, rng_state = self.core.sample_clustering(alphas, ds, rng_state)
@@ -434,6 +448,18 @@ def sweep_sequential_many(engines, row_begin, row_end, rng_states):
     list.  -> the new rng states (numpy uint32)."""
     return _core.sweep_sequential_many([g.core for g in engines], row_begin,
                                        row_end, rng_states)
+
+
+def sample_hypers_pass_many(engines, feature, grids, rng_states, coords=None):
+    """Gibbs.sample_hypers_pass on M engines -- `Gibbs` objects whose feature
+    `feature` is DirichletDiscrete of one dim -- in the same two launches,
+    engine i with rng_states[i]; the grid's accumulator chains are shared.
+    -> (indices uint32 [M, n_coords], the new rng states uint32 [M])"""
+    indices, states = _core.sample_hypers_pass_many(
+        [g.core for g in engines], feature, grids, rng_states, coords)
+    for g in engines:
+        g.shareds[feature] = g.core.shared(feature)
+    return indices, states
 
 
 PREDICT_MANY_DRAW_ALL = _core.PREDICT_MANY_DRAW_ALL
@@ -1176,6 +1202,14 @@ class ShardedGibbs(object):
     def sample_hypers(self, feature, shareds, rng_state):
         self._whole()
         return self.backend.sample_hypers(feature, list(shareds), rng_state)
+
+    def sample_hypers_pass(self, feature, grids, rng_state, coords=None):
+        """Every rank calls it alike: the chains are summed in a fixed order,
+        so replicas with equal rng_state choose alike.  A value-partitioned
+        rank gathers its cells first."""
+        self._whole()
+        return self.backend.sample_hypers_pass(feature, grids, rng_state,
+                                               coords)
 
     def sample_clustering(self, alphas, ds, rng_state):
         return self.backend.sample_clustering(alphas, ds, rng_state)

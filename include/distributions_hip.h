@@ -1423,6 +1423,88 @@ int dist_gibbs_sample_hypers(dist_gibbs_t * g, int feature,
 int dist_gibbs_sample_clustering(dist_gibbs_t * g, const float * alphas,
                                  const float * ds, size_t n,
                                  uint32_t * rng_state, size_t * chosen);
+/* A whole coordinate pass of a DirichletDiscrete feature in one call: for
+ * every step i, a grid of grid_size values for alphas[coords[i]] is scored
+ * (MixtureSlave::score_data_grid, mixture.hpp:433-438, in DirichletDiscrete's
+ * incremental form, dd.hpp:259-284), one is drawn (sample_from_scores_
+ * overwrite, random.hpp:361-392) and takes the coordinate's place.  It is
+ * DEFINED as this loop of dist_gibbs_sample_hypers calls and gives its result
+ * bit for bit -- chosen[], the advanced *rng_state, the Shared in force
+ * afterwards and everything derived from it:
+ *
+ *     alphas = the feature's alphas in force
+ *     for i in 0 .. n_coords-1:
+ *         v = coords[i];  row = grid + i * grid_stride
+ *         candidate c = alphas with alphas[v] = row[c],  c < grid_size
+ *         dist_gibbs_sample_hypers(g, feature, candidates, grid_size,
+ *                                  rng_state, &chosen[i])
+ *         alphas[v] = row[chosen[i]]
+ *
+ * coords may be in any order and may repeat (a coordinate visited again sees
+ * its earlier draw); grid_stride == 0 gives every step the same grid_size
+ * values, otherwise grid_stride >= grid_size floats lie between the steps'
+ * rows.  Each step takes one engine step of *rng_state; n_coords == 0 changes
+ * nothing and leaves the state as given.  The loop's bit rules: candidate 0's
+ * alpha_sum is the float sum of its alphas in index order, the following ones
+ * carry it in binary64 over the changed coordinate (only where the floats
+ * differ) and narrow it; a coordinate's accumulator is the float sum over the
+ * groups with members, in index order, of fast_lgamma(a + count) -
+ * fast_lgamma(a), the shift accumulator that of fast_lgamma(alpha_sum) -
+ * fast_lgamma(alpha_sum + size); a score is vector_sum over the dim + 1
+ * accumulators in the association the reference was built with.
+ *
+ * NOT readers, like dist_gibbs_sample_hypers: they fail while a batch is open
+ * and on a value-partitioned rank with stale cells, and forget a run.
+ * Everything is checked before anything is launched or installed -- the
+ * feature index; its kind (DirichletDiscrete, otherwise the call fails naming
+ * the kind); coords[i] in [0, dim); 1 <= grid_size <= INT_MAX; every grid value
+ * finite and > 0, which a DirichletDiscrete alpha has to be; _many: engines
+ * non-null and distinct, at most 65535, the feature of one dim across them --
+ * and a refused call leaves every engine as it was.
+ *
+ * The device runs the pass in 2 launches whatever n_coords, grid_size and m
+ * are: every accumulator chain of the pass at once (one per coordinate under
+ * the alphas in force and one per distinct (coords[i], grid value), the
+ * latter shared by all engines), then one workgroup per engine that walks the
+ * steps -- alpha_sums, shift accumulators, closing sums, draw -- and leaves
+ * chosen[] and the state for the host's single wait; the final alphas are
+ * installed once per engine as dist_gibbs_set_shared does.  Where the loop's
+ * arithmetic cannot be reproduced without the host, the engine concerned runs
+ * the loop itself, whose result is the same by definition:
+ *  - an alpha_sum below 2.5 is reachable: fast_lgamma then takes glibc's
+ *    lgammaf per registered argument, and which sums occur depends on the
+ *    draws.  Decided from the binary64 sum, over the coordinates, of the
+ *    smallest value each can hold (its alpha in force, its grid values if a
+ *    step visits it): below 3.0 the loop runs.  A float sum of dim <= 256
+ *    positive terms lies within 256 * 2^-24 < 2e-5 relative of the exact one,
+ *    so from 3.0 up no float sum falls below 2.99.  Likewise, by the largest
+ *    values, above 1e9: alpha_sum plus a group size must stay clear of
+ *    fast_lgamma's 2^32 branch;
+ *  - the grid's arguments below 2.5 (value + 0, 1, 2 per distinct value, held
+ *    for the call) do not all fit the process-wide table of 16384 at once;
+ *    the loop holds one step's at a time;
+ *  - no group has a member (no groups at all included): every score is +0;
+ *    widened from "no groups" because it costs nothing to tell and the
+ *    kernels would have nothing to sum;
+ *  - grid_size > 1024 (one lane of the 1024-thread workgroup closes each
+ *    candidate) or n_coords * grid_size > 2^24.
+ * dist_gibbs_hyper_stats tells which ran: a device pass adds 1 call,
+ * n_coords * grid_size candidates, dim + the distinct grid chains + n_coords *
+ * grid_size shift chains, and 2 launches, on every engine it served; the loop
+ * adds what its dist_gibbs_sample_hypers calls add, 1 call and 3 launches per
+ * step.  On sharded engines every rank calls it alike; the chains are summed
+ * in a fixed order, so replicas with equal rng_state choose alike. */
+int dist_gibbs_sample_hypers_pass(dist_gibbs_t * g, int feature,
+        const int * coords, size_t n_coords,
+        const float * grid, size_t grid_size,
+        size_t grid_stride, /* 0: one grid for every step */
+        uint32_t * rng_state, uint32_t * chosen /* [n_coords] */);
+/* ... of m engines in the same 2 launches, engine j with rng_states[j], into
+ * chosen[j * n_coords + i]; engines that need the loop run it one by one. */
+int dist_gibbs_sample_hypers_pass_many(dist_gibbs_t * const * engines, size_t m,
+        int feature, const int * coords, size_t n_coords,
+        const float * grid, size_t grid_size, size_t grid_stride,
+        uint32_t * rng_states /* [m] */, uint32_t * chosen /* [m][n_coords] */);
 /* since creation: out[0] = accumulator chains run by DirichletDiscrete grids,
  * out[1] = candidates scored, out[2] = kernel launches of this section,
  * out[3] = calls of its scoring, set and sample entry points (does not close
