@@ -1793,8 +1793,8 @@ cdef class GibbsEngine:
 
     def debug_counts(self):
         """dict of the engine's path diagnostics (dist_gibbs_debug_counts)"""
-        cdef uint64_t out[16]
-        check(dist_gibbs_debug_counts(self.ptr, out, 16))
+        cdef uint64_t out[18]
+        check(dist_gibbs_debug_counts(self.ptr, out, 18))
         return {"value_sorted_batches": out[0], "other_batches": out[1],
                 "band_launches": out[2], "running_sum_launches": out[3],
                 "band_values_last": out[4], "handed_over_last": out[5],
@@ -1802,7 +1802,8 @@ cdef class GibbsEngine:
                 "narrow_batches": out[8], "scratch_batches": out[9],
                 "fold_batches": out[10], "scan_batches": out[11],
                 "merged_batches": out[12], "fused_batches": out[13],
-                "resumed_runs": out[14], "chain_launches": out[15]}
+                "resumed_runs": out[14], "chain_launches": out[15],
+                "rows_folded_last": out[16], "rows_instance_last": out[17]}
 
     def chain_launches(self):
         """launches of the exact-chain kernel this engine issued"""

@@ -1492,6 +1492,10 @@ struct Gibbs {
         return *fold_cache.back();
     }
     uint64_t scratch_batches = 0;
+    // the last k_rows_scratch launch: ops folded, instance (0 generic, 1 GN,
+    // 2 N, 3 NN, 4 G, 5 C)
+    uint64_t rows_folded_last = 0;
+    uint64_t rows_instance_last = 0;
     DeviceBuf<int> vsArg;
     DeviceBuf<uint32_t> deferred, deferred_count;
     uint64_t stream_batches = 0;
@@ -1518,6 +1522,9 @@ struct Gibbs {
     // running sums switched on, and whether the last one did
     uint64_t band_batches = 0, prefix_batches = 0;
     bool last_bands = false, last_prefix = false;
+    // entries of vsBandMode that launch used: one per value, or (a fused
+    // batch) one per apply chunk -- which can be fewer than the values
+    uint32_t last_band_count = 0;
 
     // Device-side normalisation of the group set (k_normalise): a whole sweep
     // is queued without the host looking at the group sizes in between.
@@ -2901,6 +2908,8 @@ struct Gibbs {
         HIP_CHECK(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(block),
                                   args, 0, stream()));
         scratch_batches += 1;
+        rows_folded_last = (uint64_t)F.n;
+        rows_instance_last = (uint64_t)shape_id;
         return true;
     }
 
@@ -3550,6 +3559,7 @@ struct Gibbs {
             vsBandTile.reserve(band_count, 0);
         }
         last_bands = bands;
+        last_band_count = bands ? band_count : 0;
         last_prefix = prefix;
         band_batches += bands ? 1 : 0;
         prefix_batches += prefix ? 1 : 0;
@@ -9448,16 +9458,20 @@ int dist_gibbs_path_counts(const dist_gibbs_t * g, uint64_t * value_sorted,
 int dist_gibbs_debug_counts(dist_gibbs_t * g, uint64_t * out, size_t n) {
     return guarded([&] {
         Gibbs & e = *g->impl.read();
-        uint64_t v[16] = {e.vs_batches, e.generic_batches, e.band_batches,
+        uint64_t v[18] = {e.vs_batches, e.generic_batches, e.band_batches,
                           e.prefix_batches, 0, 0, e.stream_batches,
                           e.run.async_batches, e.narrow_batches,
                           e.scratch_batches, e.fold_batches, e.scan_batches,
                           e.merged_batches, e.fused_batches, e.run.resumed_runs,
-                          e.chain_launches};
+                          e.chain_launches, e.rows_folded_last,
+                          e.rows_instance_last};
         if (e.last_bands && !e.batch_open && e.vsBandMode.p) {
             // values whose arg-max group's rows had a tile of their own in
             // the last value-sorted launch
-            std::vector<int> mode((size_t)e.vs_nvals());
+            // (a fused batch keeps one entry per apply chunk, not per value:
+            // read what the launch wrote, never e.vs_nvals() entries)
+            std::vector<int> mode(std::min<size_t>(e.last_band_count,
+                                                   e.vsBandMode.cap));
             e.vsBandMode.download(mode.data(), mode.size());
             for (int m : mode) v[4] += m != 0;
         }
@@ -9466,7 +9480,7 @@ int dist_gibbs_debug_counts(dist_gibbs_t * g, uint64_t * out, size_t n) {
             e.deferred_count.download(&d, 1);
             v[5] = d;
         }
-        for (size_t i = 0; i < n && i < 16; ++i) out[i] = v[i];
+        for (size_t i = 0; i < n && i < 18; ++i) out[i] = v[i];
     });
 }
 int dist_gibbs_phase_stats(dist_gibbs_t * g, double ms_out[5],

@@ -1307,7 +1307,7 @@ int dist_gibbs_set_option(dist_gibbs_t * g, const char * name, int value);
 /* how many batches each score+sample kernel has served */
 int dist_gibbs_path_counts(const dist_gibbs_t * g, uint64_t * value_sorted,
                            uint64_t * generic);
-/* diagnostics for the tests: out[0..15] = batches through the value-sorted
+/* diagnostics for the tests: out[0..17] = batches through the value-sorted
  * kernel, through the other kernels, launches with band tiles on, launches
  * with running sums on, values whose arg-max rows had their own tile in the
  * last value-sorted launch, rows that launch handed to the wave-per-row
@@ -1317,8 +1317,12 @@ int dist_gibbs_path_counts(const dist_gibbs_t * g, uint64_t * value_sorted,
  * folded leading features, batches sampled in scan mode, batches with merged
  * float statistics, batches whose group set, caches and tables came from the
  * one fused launch, sharded runs this rank closed between two passes and took
- * up again, launches of the exact-chain kernel k_chains this engine issued
- * (first min(n, 16) entries are written) */
+ * up again, launches of the exact-chain kernel k_chains this engine issued,
+ * out[16] the leading ops the last k_rows_scratch launch folded into its
+ * per-(joint value, group) table, out[17] the instance that launch took by
+ * the ops that remained (0 generic, 1 GN, 2 N, 3 NN, 4 G, 5 C; G a table
+ * gather, C a categorical, N a NormalInverseChiSq); both 0 before any such
+ * launch (first min(n, 18) entries are written) */
 int dist_gibbs_debug_counts(dist_gibbs_t * g, uint64_t * out, size_t n);
 /* "phase_timing" = 1 (a diagnostic: six events per sub-sweep): HIP-event time
  * (ms, summed) of the five phases of the device-normalised value-sorted

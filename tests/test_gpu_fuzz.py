@@ -31,6 +31,28 @@ def test_differential_fuzz_large(first):
     assert not failures, failures
 
 
+@pytest.mark.parametrize("first", [700000])
+def test_differential_fuzz_wide(first):
+    """tools/fuzz.py wide: lists of four to eight features, 2500 to 9000
+    rows, batches of 333, 4096 or all rows.  The slice must not be thin: at
+    least ten of its thirty seeds end with batches through k_rows_scratch
+    (measured: 22 -- all but 700005, 700008, 700014, 700016, 700020, 700021,
+    700025, 700026; the draws decide: debug.rows_scratch is 0 one time in
+    four, and batches of 333 rows go to the wave-per-row kernel)."""
+    import fuzz
+    failures, reached = [], []
+    for seed in range(first, first + 30):
+        err = fuzz.trial(seed, wide=True)
+        if err:
+            failures.append(err)
+        elif (fuzz.LAST["features"] > 3
+              and fuzz.LAST["counts"]["scratch_batches"] > 0):
+            reached.append(seed)
+    print("k_rows_scratch with more than three features: seeds", reached)
+    assert not failures, failures
+    assert len(reached) >= 10, reached
+
+
 @pytest.mark.parametrize("seed", [501609])
 def test_fuzz_seeds_that_once_failed(seed):
     """501609: a fused batch whose group set was closed by k_normalise (the

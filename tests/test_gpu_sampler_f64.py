@@ -18,6 +18,7 @@ import pytest
 
 import f64_sampling as fs
 import oracle_lib as ol
+import wide_rows
 import workloads
 
 pytestmark = pytest.mark.gpu
@@ -130,6 +131,17 @@ CASES = {
     "scratch_scan_singletons": (
         lambda: with_singletons("gp_nich", 30000, 1024), ROWS_SCAN,
         {"scratch_batches": 1}, "rows_scan"),
+    # long lists (tests/wide_rows.py): rows_score_lane's loop over up to
+    # eight ops, unfolded (wide8: eight ops) and behind a fold of four
+    # (mixed5: NormalInverseChiSq alone remains)
+    "scratch_scan_wide8": (lambda: wide_rows.make("wide8", 6000, 64),
+                           ROWS_SCAN, {"scratch_batches": 1,
+                                       "rows_folded_last": 0}, "rows_scan"),
+    "scratch_scan_mixed5_fold": (
+        lambda: wide_rows.make("mixed5", 6000, 64),
+        dict(ROWS_SCAN, **{"debug.rows_fold": 2}),
+        {"scratch_batches": 1, "fold_batches": 1, "rows_folded_last": 4,
+         "rows_instance_last": 2}, "rows_scan"),
     "program_kernel": (("gp_nich", 20000, 65), dict(ROWS, **{
         "debug.rows_scratch": 0}), {"scratch_batches": 0, "fold_batches": 0,
                                     "value_sorted_batches": 0}, "exact"),

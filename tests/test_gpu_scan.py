@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 from scipy import stats
 
+import wide_rows
 import workloads
 
 pytestmark = pytest.mark.gpu
@@ -30,7 +31,10 @@ CONFIGS = ["gp_nich", "nich", "nich2", "dd_bb_gp", "gp", "dd", "bnb"]
 def engine_for(config, n, k, sampling, fold=1, seed=workloads.SEED,
                extra_rows=None, value_sorted=0):
     from distributions_amd import engine
-    osh, gsh, vals, assign = workloads.make(config, n, k, seed=seed)
+    if config in wide_rows.LISTS:     # the long lists of tests/wide_rows.py
+        osh, gsh, vals, assign = wide_rows.make(config, n, k)
+    else:
+        osh, gsh, vals, assign = workloads.make(config, n, k, seed=seed)
     if extra_rows is not None:
         count, values, group = extra_rows
         vals = [np.concatenate([v, np.full(count, x, v.dtype)])
@@ -44,7 +48,7 @@ def engine_for(config, n, k, sampling, fold=1, seed=workloads.SEED,
     return gpu, vals, assign
 
 
-@pytest.mark.parametrize("config", CONFIGS)
+@pytest.mark.parametrize("config", CONFIGS + ["wide8", "mixed5"])
 @pytest.mark.parametrize("k", [24, 101])
 def test_scan_agrees_with_exact_on_one_batch(config, k):
     n = 50000

@@ -1,6 +1,7 @@
 """Differential fuzzing of the engine against the oracle: random feature lists,
 hyper-parameters, clustering models, group sets, batch tilings, kernel choices
-and interleaved sequential stretches.  usage: fuzz.py [trials] [first_seed]"""
+and interleaved sequential stretches.
+usage: fuzz.py [trials] [first_seed] [collective | large | wide]"""
 import ctypes
 import os
 import sys
@@ -34,7 +35,14 @@ def same_state(orc, gpu):
     return None
 
 
-def trial(seed, large=False):
+# what the last trial ran: its feature count and the engine's debug_counts()
+LAST = {}
+
+
+def trial(seed, large=False, wide=False):
+    """wide: lists of four to eight features over batches large enough for
+    the general-row kernels (k_rows_scratch, k_sweep_program); its extra
+    draws are taken only then, so every other seed keeps its meaning"""
     rng = np.random.default_rng(seed)
     L = ol.oracle()
     L.orc_mix_set_low_entropy.restype = None
@@ -46,8 +54,13 @@ def trial(seed, large=False):
         k = int(rng.choice([250, 1000, 3000, 8192]))
         if k == 8192:   # (the oracle does 12 k row-updates/s there)
             n = 20000
+    if wide:
+        n = int(rng.choice([2500, 5000, 9000]))
+        k = int(rng.choice([1, 2, 7, 33, 150]))
     empty = int(rng.integers(1, 4))
     nf = int(rng.choice([1, 1, 1, 2, 3]))
+    if wide:
+        nf = int(rng.integers(4, 9))
     feats_o, feats_g, vals, desc = [], [], [], []
     for _ in range(nf):
         kind = rng.choice(["dd", "bb", "gp", "nich", "bnb", "dpd"])
@@ -152,6 +165,8 @@ def trial(seed, large=False):
             batch = int(rng.choice([1, 7, 64, 333, 4096, n]))
             if large:
                 batch = int(rng.choice([4096, 20000, n]))
+            if wide:
+                batch = int(rng.choice([333, 4096, n]))
             for b0 in range(0, n, batch):
                 orc.gibbs_batch(b0, min(n, b0 + batch), st, draw)
             gpu.sweep(0, n, batch, eng_seed, draw_base=draw)
@@ -162,6 +177,11 @@ def trial(seed, large=False):
             err = same_state(orc, gpu)
             if err:
                 return what + " step %d: %s" % (step, err)
+    # (the diagnostics are part of what is fuzzed: band_values_last once
+    # copied more entries than a fused batch's band table holds -- seeds
+    # 2000-2039 and 501609)
+    LAST.clear()
+    LAST.update(features=nf, counts=gpu.core.debug_counts())
     return None
 
 
@@ -237,6 +257,7 @@ def main():
     first = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     collective = len(sys.argv) > 3 and sys.argv[3] == "collective"
     large = len(sys.argv) > 3 and sys.argv[3] == "large"
+    wide = len(sys.argv) > 3 and sys.argv[3] == "wide"
     if collective:
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -246,7 +267,7 @@ def main():
     for seed in range(first, first + trials):
         try:
             err = (trial_collective(seed) if collective
-                   else trial(seed, large=large))
+                   else trial(seed, large=large, wide=wide))
         except Exception as e:   # noqa: BLE001
             err = "seed %d: exception %r" % (seed, e)
         if err:
