@@ -3340,8 +3340,9 @@ struct Gibbs {
         remap_log.reserve((size_t)kRemapEpochs * kRemapEntry, 0);   // zeros
         A.remap_log = remap_log.p;
         A.k_limit = T.Kuse;
-        launch_lds<&k_vs_tables<KIND>>(dim3(T.n_values), dim3(kTablesBlock),
-                                       vs_tables_lds(T.Kpad), A, T);
+        launch_lds<&k_vs_tables<KIND>>(
+            dim3(T.n_values), dim3(kTablesBlock),
+            vs_tables_lds(T.Kuse, vs_tables_staged(T.Kuse)), A, T);
         run.finish_pending = false;   // (this launch normalised the group set)
         base_valid = true;
         P.feat[0] = f.view();

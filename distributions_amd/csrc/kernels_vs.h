@@ -528,14 +528,29 @@ __device__ __forceinline__ void vs_tables_totals(
     }
 }
 
-// (LDS: four words per group of the padded bound, see tb_lds below)
-constexpr size_t vs_tables_lds(int Kpad) { return ((size_t)Kpad * 4 + 2) * 4; }
+// LDS: four words per group of the LAUNCH's bound on the group count (Klds =
+// VsTables::Kuse, see tb_lds below), rounded up to 16 bytes; behind them,
+// where the whole stays within kLdsWorkgroupLimit, copies of the
+// exponential's and the logarithm's tables (a launch bound above some 4 800
+// groups reads the global ones).
+constexpr int kTablesExpWords = 1024, kTablesLogWords = 16384;
+constexpr size_t kTablesStagedWords = kTablesExpWords + kTablesLogWords;
+constexpr size_t vs_tables_strip_words(int Klds) {
+    return ((size_t)Klds * 4 + 2 + 3) & ~(size_t)3;
+}
+constexpr size_t vs_tables_lds(int Klds, bool staged) {
+    return (vs_tables_strip_words(Klds) + (staged ? kTablesStagedWords : 0)) * 4;
+}
+constexpr bool vs_tables_staged(int Klds) {
+    return vs_tables_lds(Klds, true) <= kLdsWorkgroupLimit;
+}
 template <int KIND>
 __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
                                                             VsTables T) {
-    // [Kpad] LA | [Kpad] LB for the running sums | the plan of a batch that
-    // swap-removes groups: [Kpad + 2] vanished-before | [Kpad] the slot each
-    // slot's group comes from
+    // [Klds] LA | [Klds] LB for the running sums | the plan of a batch that
+    // swap-removes groups: [Klds + 2] vanished-before | [Klds] the slot each
+    // slot's group comes from | (staged) the exponential's table | the
+    // logarithm's
     extern __shared__ __attribute__((aligned(16))) float tb_lds[];
     constexpr int kWaves = kTablesBlock / 64;
     __shared__ float r_m1[kWaves], r_m2[kWaves];
@@ -543,11 +558,19 @@ __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
     __shared__ int s_sum[2][kWaves];
     __shared__ float sh_so;
     __shared__ int s_log[kRemapEpochs * kRemapEntry];
-    const int Kpad = T.Kpad;
+    const int Kpad = T.Kpad;   // the global vectors' row stride
+    const int Klds = T.Kuse;   // the strips in LDS
     const uint32_t x = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     SlaveView v = A.feat;
     v.kind = KIND;
+    const bool staged = vs_tables_staged(Klds);
+    uint32_t * lds_exp =
+        reinterpret_cast<uint32_t *>(tb_lds) + vs_tables_strip_words(Klds);
+    uint32_t * lds_log = lds_exp + kTablesExpWords;
+    // (wave-uniform: one instantiation reads either source)
+    const uint32_t * exp_tab = staged ? lds_exp : g_tables_dev.exp_table;
+    const uint32_t * log_tab = staged ? lds_log : g_tables_dev.log_table;
     // ---- everything the kernel reads per group, in ONE trip to memory: the
     // loads assume that no group vanished (slot k's group stays in slot k),
     // the usual case; a batch that swap-removed groups reads again below
@@ -566,13 +589,55 @@ __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
         }
     }
     // (the log of earlier batches' moves, for the bands at the end)
-    if (T.band_mode)
-        for (int i = tid; i < kRemapEpochs * kRemapEntry; i += kTablesBlock)
-            s_log[i] = A.remap_log[i];
+    static_assert(kRemapEpochs * kRemapEntry <= kTablesBlock, "a word each");
+    int log_word = 0;
+    if (T.band_mode && tid < kRemapEpochs * kRemapEntry)
+        log_word = A.remap_log[tid];
+    // ... and the two tables' copies, 16 bytes a lane, behind those loads:
+    // they are under way while the plan's sums wait for the group sizes, and
+    // land in LDS in front of the barrier that follows the sums.  (The
+    // compiler may not move them to the front of that trip -- it did -- and
+    // the scalars below, which the kernel waits for at once, come after.)
+    asm volatile("" ::: "memory");
+    constexpr int kLogQuads = kTablesLogWords / 4 / kTablesBlock;
+    static_assert(kLogQuads * 4 * kTablesBlock == kTablesLogWords
+                      && kTablesExpWords / 4 <= kTablesBlock, "whole rounds");
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    v4u tq_log[kLogQuads], tq_exp = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int q = 0; q < kLogQuads; ++q) tq_log[q] = tq_exp;
+    if (staged) {
+        const v4u * src =
+            reinterpret_cast<const v4u *>(g_tables_dev.log_table);
+#pragma unroll
+        for (int q = 0; q < kLogQuads; ++q)
+            tq_log[q] = src[tid + q * kTablesBlock];
+        if (tid < kTablesExpWords / 4)
+            tq_exp =
+                reinterpret_cast<const v4u *>(g_tables_dev.exp_table)[tid];
+    }
+    asm volatile("" ::: "memory");
     const float prior_x = is_cat(KIND) ? v.prior[x] : 0.f;
     const int K0 = A.dev_in->K;
     const uint32_t global_size0 = A.dev_in->global_size;
     const uint32_t epoch0 = (uint32_t)A.dev_in->pad;
+    // (the band section's words, see the end: the value's chunks and where
+    // its rows begin with this trip, the last wave's first chunk's stamp and
+    // group count as soon as the chunk is known)
+    uint32_t band_c0 = 0u, band_c1 = 0u, band_pos0 = 0u, band_then = 0u;
+    int band_k_then = 0;
+    if (T.band_mode) {
+        band_c0 = T.chunk_first[x];
+        band_c1 = T.chunk_first[x + 1];
+        band_pos0 = T.val_start[x];
+    }
+    if (T.band_mode && wave == kWaves - 1 && A.offsets.off
+        && band_c0 + lane < band_c1) {
+        const uint32_t c = band_c0 + lane;
+        band_then = A.offsets.epoch[c];
+        band_k_then =
+            A.offsets.off[(size_t)c * A.offsets.stride + A.offsets.stride - 1];
+    }
     // ---- the plan: vanished and filled groups since the last batch's entry
     int removed = 0, n_created = 0;
     {
@@ -591,6 +656,16 @@ __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
             c_sum += __shfl_xor(c_sum, off);
         }
         if (lane == 0) { s_sum[0][wave] = e_sum; s_sum[1][wave] = c_sum; }
+        if (T.band_mode && tid < kRemapEpochs * kRemapEntry)
+            s_log[tid] = log_word;
+        if (staged) {
+            v4u * dst = reinterpret_cast<v4u *>(lds_log);
+#pragma unroll
+            for (int q = 0; q < kLogQuads; ++q)
+                dst[tid + q * kTablesBlock] = tq_log[q];
+            if (tid < kTablesExpWords / 4)
+                reinterpret_cast<v4u *>(lds_exp)[tid] = tq_exp;
+        }
         __syncthreads();
 #pragma unroll
         for (int w = 0; w < kWaves; ++w) {
@@ -602,8 +677,8 @@ __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
     const int k_new = size;
     const int K1 = size + n_created;
     const int nonempty = K1 - A.n_empty;
-    int * before = reinterpret_cast<int *>(tb_lds + 2 * (size_t)Kpad);
-    int * src_of = before + Kpad + 2;
+    int * before = reinterpret_cast<int *>(tb_lds + 2 * (size_t)Klds);
+    int * src_of = before + Klds + 2;
     auto emptied_at = [&](int k) {
         return A.snap_in[k] > 0 && A.counts_in[k] == 0;
     };
@@ -671,10 +746,11 @@ __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
     // pass 1), its own-slot score; appended groups are empty (Group::init,
     // dd.hpp:113-121)
     const bool owner = x == 0;
-    const float shift = py_shift(A.sample_size - 1, A.alpha);
-    const float empty_score = py_empty_score(A.alpha, A.d, nonempty, A.n_empty);
+    const float shift = py_shift_t(A.sample_size - 1, A.alpha, log_tab);
+    const float empty_score =
+        py_empty_score_t(A.alpha, A.d, nonempty, A.n_empty, log_tab);
     const float empty_single =
-        py_empty_score(A.alpha, A.d, nonempty - 1, A.n_empty);
+        py_empty_score_t(A.alpha, A.d, nonempty - 1, A.n_empty, log_tab);
     const float lf = KIND == DIST_GP ? fast_log_factorial(x) : 0.f;
     float sc[kTablesPer], so[kTablesPer];
     float m1 = -INFINITY, m2 = -INFINITY;
@@ -695,13 +771,14 @@ __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
         const int c = cell[e];
         Entry en = {0.f, 0.f, 0.f, 0.f};
         if (is_cat(KIND)) {
-            en.c0 = fast_log(v.alpha_sum + (float)st.i0);
-            en.c1 = fast_log(prior_x + (float)c);
+            en.c0 = fast_log_t(v.alpha_sum + (float)st.i0, log_tab);
+            en.c1 = fast_log_t(prior_x + (float)c, log_tab);
             v.S[(size_t)x * v.cap + k] = en.c1;
         } else {
             en = scorer_init(KIND, v.p, st);
         }
-        const float shifted = n ? py_nonempty_score(n, A.d) : empty_score;
+        const float shifted =
+            n ? py_nonempty_score_t(n, A.d, log_tab) : empty_score;
         const float base = shifted + shift;
         const float s = accumulate(KIND, base, en, x, lf, v.p);
         sc[e] = s;
@@ -720,15 +797,16 @@ __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
         } else if (n >= 2 && has) {
             Entry er = {0.f, 0.f, 0.f, 0.f};
             if (is_cat(KIND)) {
-                er.c0 = fast_log(v.alpha_sum + (float)(st.i0 - 1));
-                er.c1 = fast_log(prior_x + (float)(c - 1));
+                er.c0 = fast_log_t(v.alpha_sum + (float)(st.i0 - 1), log_tab);
+                er.c1 = fast_log_t(prior_x + (float)(c - 1), log_tab);
             } else {
                 Stats s2 = st;
                 stats_remove(KIND, s2, x);
                 er = scorer_init(KIND, v.p, s2);
             }
-            so[e] = accumulate(KIND, py_nonempty_score(n - 1, A.d) + shift,
-                               er, x, lf, v.p);
+            so[e] = accumulate(
+                KIND, py_nonempty_score_t(n - 1, A.d, log_tab) + shift, er, x,
+                lf, v.p);
         }
         if (owner) {
             A.counts_out[k] = n;
@@ -788,7 +866,7 @@ __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
     float * la = T.LA + (size_t)x * Kpad;
     float * lb = T.LB + (size_t)x * Kpad;
     float * lds_a = tb_lds;
-    float * lds_b = tb_lds + Kpad;
+    float * lds_b = tb_lds + Klds;
     // (the totals' own-slot likelihoods: where the plan's vanished-before
     // counts were, read for the last time before the barrier behind src_of)
     float * lds_o = reinterpret_cast<float *>(before);
@@ -796,15 +874,16 @@ __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
     const bool chains = T.PA != nullptr || totals;
     // (the tiles read whole chunks of kVsUnroll entries up to the group count:
     // that far the vectors are written, zeros behind the last group)
-    const int Kw = min(Kpad, (K1 + kVsUnroll - 1) / kVsUnroll * kVsUnroll);
+    // (Klds: a multiple of kVsUnroll, no less than the launch's group count)
+    const int Kw = min(Klds, (K1 + kVsUnroll - 1) / kVsUnroll * kVsUnroll);
 #pragma unroll
     for (int e = 0; e < kTablesPer; ++e) {
         const int k = tid + e * kTablesBlock;
         if (k >= Kw) continue;
         float a = 0.f, b = 0.f, o = -1.f;
         if (k < K1) {
-            a = fast_exp_nonpos(sc[e] - M, g_tables_dev.exp_table, ea, eb);
-            b = fast_exp_nonpos(sc[e] - mB, g_tables_dev.exp_table, ea, eb);
+            a = fast_exp_nonpos(sc[e] - M, exp_tab, ea, eb);
+            b = fast_exp_nonpos(sc[e] - mB, exp_tab, ea, eb);
             // the row's own-slot likelihood (k_vs_sample's set-up): -1 = the
             // row is handed over (alone in its group, or its own score above
             // the value's maximum through table rounding)
@@ -812,8 +891,8 @@ __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
             if (s_own != INFINITY && s_own != -INFINITY) {
                 const bool class_b = k == amax;
                 if (class_b || !(s_own > M))
-                    o = fast_exp_nonpos(s_own - (class_b ? mB : M),
-                                        g_tables_dev.exp_table, ea, eb);
+                    o = fast_exp_nonpos(s_own - (class_b ? mB : M), exp_tab,
+                                        ea, eb);
             }
         }
         la[k] = a;
@@ -879,29 +958,48 @@ __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
             st.pad = (int)(epoch0 + (removed > 0 ? 1u : 0u));
             *A.dev_out = st;
             A.scalars->shift = shift;
-            A.scalars->shift_full = py_shift(A.sample_size, A.alpha);
+            A.scalars->shift_full =
+                py_shift_t(A.sample_size, A.alpha, log_tab);
             A.scalars->empty_single = empty_single;
         }
     }
+    if (!chains && !T.band_mode) return;
+    // (the barrier that starts the fold: LA, LB and the own slots are in LDS)
+    __syncthreads();
     // ---- the arg-max group's band of rows in each of the value's chunks
     // (VsTables::band_tile), from the offsets the chunk's last sort left,
     // under the index the group had then (the moves since: this batch's plan,
-    // then the log, newest first)
-    if (T.band_mode) {
-        __syncthreads();   // (s_log)
-        const uint32_t c0 = T.chunk_first[x], c1 = T.chunk_first[x + 1];
-        for (uint32_t c = c0 + tid; c < c1; c += kTablesBlock) {
-            const uint32_t pos = T.val_start[x] + (c - c0) * (uint32_t)kVsApplyRows;
+    // then the log, newest first).  The workgroup's LAST wave does it, beside
+    // the others' fold jobs and ahead of its own (it has one from 1 920
+    // groups on); what it reads from LDS -- src_of, s_log -- was there at the
+    // barrier above, and nothing below waits for it.  Its first chunk's stamp
+    // and group count were asked for at the top; only the band's two offsets
+    // wait for the arg-max group.
+    if (T.band_mode && wave == kWaves - 1) {
+        bool first = true;
+        for (uint32_t c = band_c0 + lane; c < band_c1; c += 64) {
+            const uint32_t pos =
+                band_pos0 + (c - band_c0) * (uint32_t)kVsApplyRows;
             int mode = 0;
             VsTile band = VsTile{x, 0u, 0u, c};
-            const uint32_t then = A.offsets.off ? A.offsets.epoch[c] : 0u;
+            // (no offsets recorded: never formed, never read)
+            const int * off =
+                A.offsets.off ? A.offsets.off + (size_t)c * A.offsets.stride
+                              : nullptr;
+            uint32_t then = band_then;
+            int k_then = band_k_then;
+            if (!first) {
+                then = off ? A.offsets.epoch[c] : 0u;
+                k_then = off ? off[A.offsets.stride - 1] : 0;
+            }
+            first = false;
             // (values of several chunks -- Zipf's head -- keep to their
             // regular tiles: a band tile per chunk of theirs was measured,
             // k_vs_sample 105 against 86 us on Zipf(1.1) values: forty more
             // tiles of full chain length for a handful of rows each, ahead
             // of everything else in the launch)
             if (then != 0u && epoch0 - then < (uint32_t)kRemapEpochs
-                && c1 - c0 == 1) {
+                && band_c1 - band_c0 == 1) {
                 // the arg-max group's index when the chunk was sorted; -1: it
                 // did not exist then (no rows of it here)
                 bool known = true;
@@ -923,8 +1021,6 @@ __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
                     }
                 }
                 if (known) {
-                    const int * off = A.offsets.off + (size_t)c * A.offsets.stride;
-                    const int k_then = off[A.offsets.stride - 1];
                     uint32_t lo = 0u, hi = 0u;
                     if (a >= 0 && a < k_then) {
                         lo = (uint32_t)off[a];
@@ -941,7 +1037,6 @@ __global__ __launch_bounds__(kTablesBlock) void k_vs_tables(TablesParams A,
         }
     }
     if (!chains) return;
-    __syncthreads();
     if (totals) {
         vs_tables_totals(T.tot + (size_t)x * Kpad, lds_a, lds_b, lds_o, K1, Kw,
                          amax, wave, lane);

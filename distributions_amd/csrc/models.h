@@ -499,17 +499,29 @@ DIST_HD double py_score_counts_term(float alpha, float d, int count,
 }
 
 // Clustering<int>::PitmanYor cached scores (clustering.hpp:215-230)
-DIST_HD float py_nonempty_score(int count, float d) {
-    return fast_log((float)count - d);
+// (the _t forms take the logarithm's table, which may be a copy in LDS)
+DIST_HD float py_nonempty_score_t(int count, float d, const uint32_t * table) {
+    return fast_log_t((float)count - d, table);
 }
-DIST_HD float py_empty_score(float alpha, float d, int nonempty, int empty) {
+DIST_HD float py_nonempty_score(int count, float d) {
+    return py_nonempty_score_t(count, d, tables().log_table);
+}
+DIST_HD float py_empty_score_t(float alpha, float d, int nonempty, int empty,
+                               const uint32_t * table) {
     const float numer = alpha + d * (float)nonempty;
     const float denom = (float)empty;
-    return fast_log(numer / denom);
+    return fast_log_t(numer / denom, table);
+}
+DIST_HD float py_empty_score(float alpha, float d, int nonempty, int empty) {
+    return py_empty_score_t(alpha, d, nonempty, empty, tables().log_table);
 }
 // clustering.hpp:202: shift = -fast_log(sample_size + alpha)
+DIST_HD float py_shift_t(long long sample_size, float alpha,
+                         const uint32_t * table) {
+    return -fast_log_t((float)(unsigned long long)sample_size + alpha, table);
+}
 DIST_HD float py_shift(long long sample_size, float alpha) {
-    return -fast_log((float)(unsigned long long)sample_size + alpha);
+    return py_shift_t(sample_size, alpha, tables().log_table);
 }
 // Clustering<int>::LowEntropy (clustering.hpp:245-331).  dataset_size is the
 // model's only parameter; nonempty_group_count does not enter its scores.

@@ -24,7 +24,8 @@ namespace dist {
 
 // Tables live in device global memory (L2-resident: 64 KiB + 4 KiB + small)
 // and in host memory; kernels that gather per lane stage the hot ones in LDS.
-struct Tables {
+// (16-byte aligned: k_vs_tables copies the first two with 16-byte loads)
+struct alignas(16) Tables {
     uint32_t log_table[16384];   // special.cc:35-44, FastLog(14)
     uint32_t exp_table[1024];    // vendor/fmath.hpp:165-172
     uint32_t lgamma_coeff5[192]; // special.cc:144-211
