@@ -259,6 +259,32 @@ cdef extern from "distributions_hip.h" nogil:
     int dist_gibbs_coassign(dist_gibbs_t *, size_t, const uint32_t * const *,
                             size_t, const uint32_t * const *, float *,
                             size_t) nogil
+    int dist_partition_agreement_dev(size_t, size_t, const uint32_t * const *,
+                                     const uint32_t *, uint64_t *,
+                                     double *) nogil
+    int dist_partition_agreement(size_t, size_t, const uint32_t * const *,
+                                 const uint32_t *, uint64_t *, double *) nogil
+    int dist_gibbs_partition_agreement_many_dev(
+        dist_gibbs_t * const *, size_t, size_t, const uint32_t * const *,
+        size_t, const uint32_t *, uint64_t *, double *) nogil
+    int dist_gibbs_partition_agreement_many(
+        dist_gibbs_t * const *, size_t, size_t, const uint32_t * const *,
+        size_t, const uint32_t *, uint64_t *, double *) nogil
+    int dist_gibbs_partition_agreement(
+        dist_gibbs_t *, size_t, const uint32_t * const *, size_t,
+        const uint32_t *, uint64_t *, double *) nogil
+    int dist_gibbs_coassign_resident_many_dev(
+        dist_gibbs_t * const *, size_t, const uint32_t *, size_t,
+        const uint32_t *, size_t, float *, size_t) nogil
+    int dist_gibbs_coassign_resident_many(
+        dist_gibbs_t * const *, size_t, const uint32_t *, size_t,
+        const uint32_t *, size_t, float *, size_t) nogil
+    int dist_gibbs_coassign_resident_dev(
+        dist_gibbs_t *, const uint32_t *, size_t, const uint32_t *, size_t,
+        float *, size_t) nogil
+    int dist_gibbs_coassign_resident(
+        dist_gibbs_t *, const uint32_t *, size_t, const uint32_t *, size_t,
+        float *, size_t) nogil
     int dist_gibbs_coassign_topk_many_dev(
         dist_gibbs_t * const *, size_t, size_t, const uint32_t * const *,
         size_t, const uint32_t * const *, size_t, unsigned, uint32_t *,
@@ -2336,6 +2362,155 @@ def coassign_many(engines, values, other=None, bint single=False):
     free(tc)
     check(rc)
     return out
+
+
+def _label_columns(columns, bint dev, size_t n_rows):
+    """-> (what keeps the columns alive, a malloc'ed array of their
+    addresses): device addresses as they are, host columns as contiguous
+    uint32 arrays of n_rows words"""
+    cdef size_t p = len(columns)
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] w
+    cdef size_t i
+    if dev:
+        return None, <size_t> _address_columns(columns)
+    words = []
+    for c in columns:
+        w = np.ascontiguousarray(c, np.uint32).reshape(-1)
+        if <size_t> w.shape[0] != n_rows:
+            raise RuntimeError("partition_agreement: a label column of %d "
+                               "rows, not %d" % (w.shape[0], n_rows))
+        words.append(w)
+    cdef const uint32_t ** cols = <const uint32_t **> malloc(
+        sizeof(void *) * (p + 1))
+    for i in range(p):
+        w = words[i]
+        cols[i] = <const uint32_t *> w.data
+    return words, <size_t> cols
+
+
+def partition_agreement_many(engines, size_t n_rows, columns, n_labels,
+                             bint nlogn=True, bint dev=False,
+                             bint single=False):
+    """sq and nlogn of the partitions (the engines' resident assignments,
+    then `columns`) of the same n_rows rows
+    (dist_gibbs_partition_agreement_many[_dev]; single:
+    dist_gibbs_partition_agreement; no engine: dist_partition_agreement[_dev]).
+    columns: host uint32 arrays, or with dev their device addresses; n_labels
+    one exclusive bound per column.
+    -> (uint64 [P, P], float64 [P, P] or None)"""
+    cdef size_t m = len(engines), x = len(columns)
+    if single and m != 1:
+        raise RuntimeError("partition_agreement: one engine")
+    if len(n_labels) != x:
+        raise RuntimeError("partition_agreement: one n_labels per column")
+    cdef size_t p = m + x
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] bounds = np.ascontiguousarray(
+        np.asarray(n_labels, np.uint32).reshape(-1))
+    cdef cnp.ndarray[cnp.uint64_t, ndim=2] sq = np.zeros((p, p), np.uint64)
+    cdef size_t pn = p if nlogn else 0
+    cdef cnp.ndarray[cnp.float64_t, ndim=2] nl = np.zeros((pn, pn),
+                                                          np.float64)
+    keep, addr = _label_columns(columns, dev, n_rows)
+    cdef const uint32_t ** cols = <const uint32_t **> <size_t> addr
+    cdef dist_gibbs_t ** ptrs
+    try:
+        ptrs = _engine_ptrs(engines)
+    except Exception:
+        free(cols)
+        raise
+    cdef uint64_t * sq_p = <uint64_t *> sq.data
+    cdef double * nl_p = NULL
+    if nlogn:
+        nl_p = <double *> nl.data
+    cdef const uint32_t * nb = <const uint32_t *> bounds.data
+    cdef int rc
+    with nogil:
+        if m == 0 and dev:
+            rc = dist_partition_agreement_dev(n_rows, x, cols, nb, sq_p, nl_p)
+        elif m == 0:
+            rc = dist_partition_agreement(n_rows, x, cols, nb, sq_p, nl_p)
+        elif dev:
+            rc = dist_gibbs_partition_agreement_many_dev(
+                <dist_gibbs_t * const *> ptrs, m, n_rows, cols, x, nb, sq_p,
+                nl_p)
+        elif single:
+            rc = dist_gibbs_partition_agreement(ptrs[0], n_rows, cols, x, nb,
+                                                sq_p, nl_p)
+        else:
+            rc = dist_gibbs_partition_agreement_many(
+                <dist_gibbs_t * const *> ptrs, m, n_rows, cols, x, nb, sq_p,
+                nl_p)
+    free(ptrs)
+    free(cols)
+    check(rc)
+    return sq, (nl if nlogn else None)
+
+
+def coassign_resident_many_dev(engines, size_t rows_a_ptr, size_t na,
+                               size_t rows_b_ptr, size_t nb, size_t out_ptr,
+                               size_t ld, bint single=False):
+    """Co-assignment of resident rows over M engines
+    (dist_gibbs_coassign_resident_many_dev; single:
+    dist_gibbs_coassign_resident_dev): device addresses of uint32 row indices
+    (rows_b_ptr 0: the rows of rows_a) and of [na, ld] floats."""
+    cdef size_t m = len(engines)
+    if single and m != 1:
+        raise RuntimeError("coassign_resident: one engine")
+    cdef dist_gibbs_t ** ptrs = _engine_ptrs(engines)
+    cdef int rc
+    with nogil:
+        if single:
+            rc = dist_gibbs_coassign_resident_dev(
+                ptrs[0], <const uint32_t *> rows_a_ptr, na,
+                <const uint32_t *> rows_b_ptr, nb, <float *> out_ptr, ld)
+        else:
+            rc = dist_gibbs_coassign_resident_many_dev(
+                <dist_gibbs_t * const *> ptrs, m,
+                <const uint32_t *> rows_a_ptr, na,
+                <const uint32_t *> rows_b_ptr, nb, <float *> out_ptr, ld)
+    free(ptrs)
+    check(rc)
+
+
+def coassign_resident_many(engines, rows, other=None, bint single=False):
+    """Co-assignment of resident rows over M engines from host index arrays
+    (dist_gibbs_coassign_resident_many; single: dist_gibbs_coassign_resident);
+    other None: the rows themselves.  -> float32 [len(rows), len(other)]"""
+    cdef size_t m = len(engines)
+    if single and m != 1:
+        raise RuntimeError("coassign_resident: one engine")
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] ra = _row_indices(rows)
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] rb = (
+        ra if other is None else _row_indices(other))
+    cdef size_t na = ra.shape[0], nb = rb.shape[0]
+    cdef cnp.ndarray[cnp.float32_t, ndim=2] out = np.zeros((na, nb),
+                                                           np.float32)
+    cdef const uint32_t * pa = <const uint32_t *> ra.data
+    cdef const uint32_t * pb = (NULL if other is None
+                                else <const uint32_t *> rb.data)
+    cdef dist_gibbs_t ** ptrs = _engine_ptrs(engines)
+    cdef int rc
+    with nogil:
+        if single:
+            rc = dist_gibbs_coassign_resident(ptrs[0], pa, na, pb, nb,
+                                              <float *> out.data, nb)
+        else:
+            rc = dist_gibbs_coassign_resident_many(
+                <dist_gibbs_t * const *> ptrs, m, pa, na, pb, nb,
+                <float *> out.data, nb)
+    free(ptrs)
+    check(rc)
+    return out
+
+
+def _row_indices(rows):
+    """row indices as a contiguous uint32 array; one that does not fit 32
+    bits is out of every engine's range"""
+    a = np.asarray(rows).reshape(-1)
+    if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+        raise RuntimeError("coassign_resident_many: row index outside the "
+                           "engines' rows")
+    return np.ascontiguousarray(a, np.uint32)
 
 
 COASSIGN_EXCLUDE_SELF = 1

@@ -6072,6 +6072,19 @@ struct Gibbs {
     static void responsibilities(dist_gibbs_t * g, size_t n,
                                  const uint32_t * const * values_dev,
                                  float * resp_dev, size_t ld);
+    // agreement of the engines' resident partitions and the co-assignment of
+    // resident rows (kernels_partitions.h; defined behind GibbsRef as well)
+    static std::vector<Gibbs *> resident_engines(
+        dist_gibbs_t * const * engines, size_t m, const std::string & who);
+    static void partition_agreement_many(
+        dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+        const uint32_t * const * extra_dev, size_t x,
+        const uint32_t * extra_n_labels, uint64_t * sq_out,
+        double * nlogn_out);
+    static void coassign_resident_many(
+        dist_gibbs_t * const * engines, size_t m, const uint32_t * rows_a_dev,
+        size_t na, const uint32_t * rows_b_dev, size_t nb, float * out_dev,
+        size_t ld);
 };
 
 }  // namespace dist
@@ -6360,6 +6373,231 @@ void dist::Gibbs::predict_many(dist_gibbs_t * const * engines, size_t m,
                  "predict_many: value outside its feature's domain at row "
                      + std::to_string(bad >> 8) + ", feature "
                      + std::to_string(bad & 0xFF));
+}
+
+// ---- partitions of resident rows (kernels_partitions.h) -------
+// sq and nlogn (may be null) of the partitions `cols` of n rows, into HOST
+// arrays of P * P entries.  Launches: one check of every column, then per
+// partition a its sort (keys for an engine's column; histogram, scan, scatter
+// -- or, past kCsMaxKeys, the library sort and its offsets), ONE
+// k_partition_pairs for every b >= a and, with nlogn, the add of its partials.
+// Two host waits: the words of the bad labels before anything trusts a label,
+// and the results.
+static void partition_agreement_cols(const std::string & who, size_t n,
+                                     const std::vector<PartitionCol> & cols,
+                                     uint64_t * sq_out, double * nlogn_out) {
+    const size_t P = cols.size();
+    if (!P || !n) return;
+    DIST_REQUIRE(sq_out != nullptr, "null argument");
+    DIST_REQUIRE(n < ((size_t)1 << 31),
+                 who + ": n_rows must be below 2^31 (a row travels through "
+                       "the sort as 2 row + 1)");
+    DIST_REQUIRE(P <= 65535, who + ": at most 65535 partitions");
+    for (size_t a = 0; a < P; ++a) {
+        DIST_REQUIRE(cols[a].labels != nullptr, "null label column");
+        DIST_REQUIRE(cols[a].n_labels <= kPartitionMaxBins,
+                     who + ": partition " + std::to_string(a) + " has "
+                         + std::to_string(cols[a].n_labels)
+                         + " labels, above the limit of "
+                         + std::to_string(kPartitionMaxBins) + " bins");
+    }
+    DeviceBuf<PartitionCol> d_cols;
+    d_cols.upload(cols.data(), P);
+    DeviceBuf<unsigned long long> bad_dev;
+    bad_dev.reserve(P, 0);
+    HIP_CHECK(hipMemsetAsync(bad_dev.p, 0xFF, P * sizeof(unsigned long long),
+                             stream()));
+    hipLaunchKernelGGL(k_partition_check,
+                       dim3(std::min(grid_for(n).x, 1024u), (unsigned)P),
+                       dim3(kBlock), 0, stream(), d_cols.p, n, bad_dev.p);
+    HIP_CHECK(hipGetLastError());
+    std::vector<unsigned long long> bad(P);
+    bad_dev.download(bad.data(), P);
+    for (size_t a = 0; a < P; ++a)
+        DIST_REQUIRE(bad[a] == ~0ull,
+                     who + ": label outside its partition's bins in "
+                           "partition " + std::to_string(a) + " at row "
+                         + std::to_string(bad[a]));
+    // (new buffers come zeroed)
+    DeviceBuf<unsigned long long> sq;
+    sq.reserve(P * P, 0);
+    DeviceBuf<double> nl, part;
+    if (nlogn_out) nl.reserve(P * P, 0);
+    DeviceBuf<uint32_t> order, keys, offset, cs_hist, cs_total, keys_sorted,
+        vals;
+    DeviceBuf<unsigned char> sort_temp;
+    order.reserve(n, 0);
+    // the bins a launch's LDS holds: the most of any b >= a
+    std::vector<uint32_t> most(P + 1, 0);
+    for (size_t a = P; a-- > 0;)
+        most[a] = std::max(most[a + 1], cols[a].n_labels);
+    for (size_t a = 0; a < P; ++a) {
+        const int k_a = (int)cols[a].n_labels;
+        const int n_keys = k_a + 1;   // (the last: k_cs_*'s padding, no rows)
+        const uint32_t * key_col = cols[a].labels;
+        if (cols[a].g2p) {
+            keys.reserve(n, 0);
+            LAUNCH(k_partition_keys, n, d_cols.p, (int)a, n, keys.p);
+            key_col = keys.p;
+        }
+        offset.reserve(grow_capacity((size_t)n_keys + 1), 0);
+        if (n_keys <= kCsMaxKeys) {
+            // rows as additions: old == nullptr, event e is row e
+            const int blocks = (int)((n + kCsEvents - 1) / kCsEvents);
+            cs_hist.reserve(grow_capacity((size_t)blocks * n_keys), 0);
+            cs_total.reserve(grow_capacity((size_t)n_keys), 0);
+            hipLaunchKernelGGL(k_cs_hist, dim3(blocks), dim3(kCsBlock),
+                               cs_hist_lds(n_keys), stream(),
+                               (const uint32_t *)nullptr, key_col, n, n_keys,
+                               cs_hist.p);
+            hipLaunchKernelGGL(k_cs_scan,
+                               dim3((n_keys + kCsBlock - 1) / kCsBlock),
+                               dim3(kCsBlock), 0, stream(), cs_hist.p, blocks,
+                               n_keys, cs_total.p);
+            launch_lds<&k_cs_scatter>(dim3(blocks), dim3(kCsBlock),
+                                      cs_scatter_lds(n_keys),
+                                      (const uint32_t *)nullptr, key_col, n,
+                                      n_keys, cs_hist.p, cs_total.p, offset.p,
+                                      order.p);
+        } else {
+            int bits = 1;
+            while ((1ull << bits) < (unsigned long long)n_keys) bits += 1;
+            keys_sorted.reserve(n, 0);
+            vals.reserve(n, 0);
+            const size_t tb = sort_pairs_temp_bytes(n, bits);
+            sort_temp.reserve(tb + 256, 0);
+            LAUNCH(k_partition_iota, n, n, vals.p);
+            sort_pairs(sort_temp.p, tb, key_col, keys_sorted.p, vals.p,
+                       order.p, n, bits, stream());
+            LAUNCH(k_partition_offsets, (size_t)n_keys + 1, keys_sorted.p, n,
+                   n_keys, offset.p);
+        }
+        const int n_b = (int)(P - a);
+        const int groups = std::min(
+            k_a, std::max(16, std::min(1024, 8192 / n_b)));
+        if (nlogn_out) part.reserve(grow_capacity((size_t)groups * n_b), 0);
+        PartitionPairs A;
+        memset(&A, 0, sizeof(A));
+        A.cols = d_cols.p;
+        A.order = order.p;
+        A.offset = offset.p;
+        A.sq = sq.p;
+        A.part = nlogn_out ? part.p : nullptr;
+        A.p = (int)P;
+        A.a = (int)a;
+        A.b0 = (int)a;
+        A.k_a = k_a;
+        A.lds_bins = most[a];
+        launch_lds<&k_partition_pairs>(dim3((unsigned)groups, (unsigned)n_b),
+                                       dim3(kBlock),
+                                       partition_pairs_lds(most[a]), A);
+        if (nlogn_out)
+            LAUNCH(k_partition_nlogn, (size_t)n_b, part.p, groups, n_b,
+                   (int)P, (int)a, (int)a, nl.p);
+    }
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "");
+    if (nlogn_out) {
+        HIP_CHECK(hipMemcpyAsync(nlogn_out, nl.p, P * P * sizeof(double),
+                                 hipMemcpyDeviceToHost, stream()));
+    }
+    sq.download(reinterpret_cast<unsigned long long *>(sq_out), P * P);
+}
+
+// dist_gibbs_assignments' rules for the engines of a call, and rows that are
+// the same data: equal counts, every row assigned
+std::vector<dist::Gibbs *> dist::Gibbs::resident_engines(
+        dist_gibbs_t * const * engines, size_t m, const std::string & who) {
+    DIST_REQUIRE(m == 0 || engines, "null argument");
+    DIST_REQUIRE(m <= 65535, who + ": at most 65535 engines");
+    std::vector<Gibbs *> e(m);
+    for (size_t i = 0; i < m; ++i) {
+        DIST_REQUIRE(engines[i], "null engine");
+        e[i] = engines[i]->impl.read();   // (settles, stays resumable)
+        for (size_t j = 0; j < i; ++j)
+            DIST_REQUIRE(e[j] != e[i], "the same engine twice");
+        DIST_REQUIRE(!e[i]->batch_open,
+                     who + ": batch open on engine " + std::to_string(i));
+        DIST_REQUIRE(e[i]->n_rows == e[0]->n_rows,
+                     who + ": engines of unequal row counts: engine "
+                         + std::to_string(i) + " holds "
+                         + std::to_string(e[i]->n_rows) + " rows, engine 0 "
+                         + std::to_string(e[0]->n_rows));
+        DIST_REQUIRE(e[i]->assigned_rows == e[i]->n_rows,
+                     who + ": engine " + std::to_string(i)
+                         + " has unassigned rows");
+    }
+    for (size_t i = 0; i < m; ++i) e[i]->flush_assign_pos();
+    return e;
+}
+
+void dist::Gibbs::partition_agreement_many(
+        dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+        const uint32_t * const * extra_dev, size_t x,
+        const uint32_t * extra_n_labels, uint64_t * sq_out,
+        double * nlogn_out) {
+    const std::string who = "partition_agreement_many";
+    DIST_REQUIRE(x == 0 || (extra_dev && extra_n_labels), "null argument");
+    const std::vector<Gibbs *> e = resident_engines(engines, m, who);
+    if (m)
+        DIST_REQUIRE(e[0]->n_rows == n_rows,
+                     who + ": n_rows is " + std::to_string(n_rows)
+                         + ", the engines hold "
+                         + std::to_string(e[0]->n_rows) + " rows");
+    std::vector<PartitionCol> cols(m + x);
+    memset(cols.data(), 0, cols.size() * sizeof(PartitionCol));
+    for (size_t i = 0; i < m; ++i) {
+        e[i]->upload_maps();
+        cols[i].labels = e[i]->assign;
+        cols[i].g2p = e[i]->d_g2p_ptr;
+        cols[i].n_global = (uint32_t)e[i]->tracker.g2p.size();
+        cols[i].n_labels = (uint32_t)e[i]->K();
+    }
+    for (size_t j = 0; j < x; ++j) {
+        cols[m + j].labels = extra_dev[j];
+        cols[m + j].n_labels = extra_n_labels[j];
+    }
+    partition_agreement_cols(who, n_rows, cols, sq_out, nlogn_out);
+}
+
+void dist::Gibbs::coassign_resident_many(
+        dist_gibbs_t * const * engines, size_t m, const uint32_t * rows_a_dev,
+        size_t na, const uint32_t * rows_b_dev, size_t nb, float * out_dev,
+        size_t ld) {
+    const std::string who = "coassign_resident_many";
+    const std::vector<Gibbs *> e = resident_engines(engines, m, who);
+    const bool sym = rows_b_dev == nullptr;
+    if (sym) {
+        rows_b_dev = rows_a_dev;
+        nb = na;
+    }
+    if (!m || !na || !nb) return;
+    DIST_REQUIRE(rows_a_dev && out_dev, "null argument");
+    DIST_REQUIRE(ld >= nb, who + ": ld is less than the column count");
+    const size_t n_rows = e[0]->n_rows;
+    std::vector<const uint32_t *> cols(m);
+    for (size_t i = 0; i < m; ++i) cols[i] = e[i]->assign;
+    DeviceBuf<const uint32_t *> d_cols;
+    d_cols.upload(cols.data(), m);
+    DeviceBuf<unsigned long long> bad_dev;
+    bad_dev.reserve(2, 0);
+    HIP_CHECK(hipMemsetAsync(bad_dev.p, 0xFF, 2 * sizeof(unsigned long long),
+                             stream()));
+    LAUNCH(k_partition_rows_check, na, rows_a_dev, na, n_rows, bad_dev.p);
+    if (!sym)
+        LAUNCH(k_partition_rows_check, nb, rows_b_dev, nb, n_rows,
+               bad_dev.p + 1);
+    LAUNCH(k_coassign_resident, na * nb, d_cols.p, (int)m, rows_a_dev, na,
+           rows_b_dev, nb, n_rows, out_dev, ld);
+    unsigned long long bad[2];
+    bad_dev.download(bad, 2);
+    DIST_REQUIRE(bad[0] == ~0ull,
+                 who + ": row index outside the engines' "
+                     + std::to_string(n_rows) + " rows at rows_a["
+                     + std::to_string(bad[0]) + "]");
+    DIST_REQUIRE(bad[1] == ~0ull,
+                 who + ": row index outside the engines' "
+                     + std::to_string(n_rows) + " rows at rows_b["
+                     + std::to_string(bad[1]) + "]");
 }
 
 // predict_many's rules for the engines of a call
@@ -9159,6 +9397,163 @@ int dist_gibbs_relate_many(dist_gibbs_t * const * engines, size_t m,
                            member_seed_state, draw_base, mi_out, stderr_out,
                            moments_out, false);
     });
+}
+// ---- partitions of resident rows --------------------------------------------
+int dist_partition_agreement_dev(size_t n_rows, size_t p,
+                                 const uint32_t * const * labels_dev,
+                                 const uint32_t * n_labels, uint64_t * sq_out,
+                                 double * nlogn_out) {
+    return guarded([&] {
+        if (!p || !n_rows) return;
+        DIST_REQUIRE(labels_dev && n_labels, "null argument");
+        ensure_device_ready();
+        std::vector<PartitionCol> cols(p);
+        memset(cols.data(), 0, p * sizeof(PartitionCol));
+        for (size_t a = 0; a < p; ++a) {
+            cols[a].labels = labels_dev[a];
+            cols[a].n_labels = n_labels[a];
+        }
+        partition_agreement_cols("partition_agreement", n_rows, cols, sq_out,
+                                 nlogn_out);
+    });
+}
+// (the host forms' columns: staged one by one, refused before any upload
+// where a length could not be a device's)
+static void stage_label_columns(const uint32_t * const * labels, size_t p,
+                                size_t n_rows,
+                                std::vector<DeviceBuf<uint32_t>> & cols,
+                                std::vector<const uint32_t *> & ptrs) {
+    cols.resize(p);
+    ptrs.assign(p + 1, nullptr);
+    for (size_t a = 0; a < p; ++a) {
+        DIST_REQUIRE(labels[a] != nullptr, "null label column");
+        cols[a].upload(labels[a], n_rows);
+        ptrs[a] = cols[a].p;
+    }
+}
+int dist_partition_agreement(size_t n_rows, size_t p,
+                             const uint32_t * const * labels,
+                             const uint32_t * n_labels, uint64_t * sq_out,
+                             double * nlogn_out) {
+    return guarded([&] {
+        if (!p || !n_rows) return;
+        DIST_REQUIRE(labels && n_labels, "null argument");
+        DIST_REQUIRE(n_rows < ((size_t)1 << 31),
+                     "partition_agreement: n_rows must be below 2^31 (a row "
+                     "travels through the sort as 2 row + 1)");
+        ensure_device_ready();
+        std::vector<DeviceBuf<uint32_t>> cols;
+        std::vector<const uint32_t *> ptrs;
+        stage_label_columns(labels, p, n_rows, cols, ptrs);
+        std::vector<PartitionCol> pc(p);
+        memset(pc.data(), 0, p * sizeof(PartitionCol));
+        for (size_t a = 0; a < p; ++a) {
+            pc[a].labels = ptrs[a];
+            pc[a].n_labels = n_labels[a];
+        }
+        partition_agreement_cols("partition_agreement", n_rows, pc, sq_out,
+                                 nlogn_out);
+    });
+}
+int dist_gibbs_partition_agreement_many_dev(
+        dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+        const uint32_t * const * extra_labels_dev, size_t x,
+        const uint32_t * extra_n_labels, uint64_t * sq_out,
+        double * nlogn_out) {
+    return guarded([&] {
+        Gibbs::partition_agreement_many(engines, m, n_rows, extra_labels_dev,
+                                        x, extra_n_labels, sq_out, nlogn_out);
+    });
+}
+int dist_gibbs_partition_agreement_many(
+        dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+        const uint32_t * const * extra_labels, size_t x,
+        const uint32_t * extra_n_labels, uint64_t * sq_out,
+        double * nlogn_out) {
+    return guarded([&] {
+        DIST_REQUIRE(x == 0 || (extra_labels && extra_n_labels),
+                     "null argument");
+        // (the engines' refusals come before any upload)
+        (void)Gibbs::resident_engines(
+            engines, m, "partition_agreement_many");
+        std::vector<DeviceBuf<uint32_t>> cols;
+        std::vector<const uint32_t *> ptrs(1, nullptr);
+        if (x && n_rows) {
+            DIST_REQUIRE(n_rows < ((size_t)1 << 31),
+                         "partition_agreement_many: n_rows must be below "
+                         "2^31 (a row travels through the sort as 2 row + 1)");
+            stage_label_columns(extra_labels, x, n_rows, cols, ptrs);
+        }
+        Gibbs::partition_agreement_many(engines, m, n_rows, ptrs.data(),
+                                        n_rows ? x : 0, extra_n_labels,
+                                        sq_out, nlogn_out);
+    });
+}
+int dist_gibbs_partition_agreement(dist_gibbs_t * g, size_t n_rows,
+                                   const uint32_t * const * extra_labels,
+                                   size_t x, const uint32_t * extra_n_labels,
+                                   uint64_t * sq_out, double * nlogn_out) {
+    return dist_gibbs_partition_agreement_many(&g, 1, n_rows, extra_labels, x,
+                                               extra_n_labels, sq_out,
+                                               nlogn_out);
+}
+int dist_gibbs_coassign_resident_many_dev(
+        dist_gibbs_t * const * engines, size_t m, const uint32_t * rows_a_dev,
+        size_t na, const uint32_t * rows_b_dev, size_t nb, float * out_dev,
+        size_t ld) {
+    return guarded([&] {
+        Gibbs::coassign_resident_many(engines, m, rows_a_dev, na, rows_b_dev,
+                                      nb, out_dev, ld);
+    });
+}
+int dist_gibbs_coassign_resident_many(
+        dist_gibbs_t * const * engines, size_t m, const uint32_t * rows_a,
+        size_t na, const uint32_t * rows_b, size_t nb, float * out,
+        size_t ld) {
+    return guarded([&] {
+        const std::string who = "coassign_resident_many";
+        const std::vector<Gibbs *> e = Gibbs::resident_engines(engines, m, who);
+        const bool sym = rows_b == nullptr;
+        if (sym) nb = na;
+        if (!m || !na || !nb) return;
+        DIST_REQUIRE(rows_a && out, "null argument");
+        DIST_REQUIRE(ld >= nb, who + ": ld is less than the column count");
+        const size_t n_rows = e[0]->n_rows;
+        for (size_t i = 0; i < na; ++i)
+            DIST_REQUIRE(rows_a[i] < n_rows,
+                         who + ": row index outside the engines' "
+                             + std::to_string(n_rows) + " rows at rows_a["
+                             + std::to_string(i) + "]");
+        for (size_t j = 0; !sym && j < nb; ++j)
+            DIST_REQUIRE(rows_b[j] < n_rows,
+                         who + ": row index outside the engines' "
+                             + std::to_string(n_rows) + " rows at rows_b["
+                             + std::to_string(j) + "]");
+        DeviceBuf<uint32_t> ra, rb;
+        ra.upload(rows_a, na);
+        if (!sym) rb.upload(rows_b, nb);
+        DeviceBuf<float> cells;
+        cells.reserve(na * nb, 0);
+        Gibbs::coassign_resident_many(engines, m, ra.p, na,
+                                      sym ? nullptr : rb.p, nb, cells.p, nb);
+        HIP_CHECK(hipMemcpy2DAsync(out, ld * sizeof(float), cells.p,
+                                   nb * sizeof(float), nb * sizeof(float), na,
+                                   hipMemcpyDeviceToHost, stream()));
+        dist::sync();
+    });
+}
+int dist_gibbs_coassign_resident_dev(dist_gibbs_t * g,
+                                     const uint32_t * rows_a_dev, size_t na,
+                                     const uint32_t * rows_b_dev, size_t nb,
+                                     float * out_dev, size_t ld) {
+    return dist_gibbs_coassign_resident_many_dev(&g, 1, rows_a_dev, na,
+                                                 rows_b_dev, nb, out_dev, ld);
+}
+int dist_gibbs_coassign_resident(dist_gibbs_t * g, const uint32_t * rows_a,
+                                 size_t na, const uint32_t * rows_b, size_t nb,
+                                 float * out, size_t ld) {
+    return dist_gibbs_coassign_resident_many(&g, 1, rows_a, na, rows_b, nb,
+                                             out, ld);
 }
 size_t dist_gibbs_group_count(const dist_gibbs_t * g) {
     size_t n = (size_t)-1;

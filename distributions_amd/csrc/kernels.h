@@ -36,3 +36,4 @@ constexpr size_t kLdsWorkgroupLimit = 144 * 1024;
 #include "kernels_vs.h"
 #include "kernels_apply.h"
 #include "kernels_hyper.h"
+#include "kernels_partitions.h"

@@ -208,6 +208,22 @@ class Gibbs(object):
         """coassign for device tensors -> a [n, n_other] tensor"""
         return _coassign_torch([self], values, other, True)
 
+    def partition_agreement(self, extra=None, nlogn=True):
+        """partition_agreement_many on this engine alone
+        (dist_gibbs_partition_agreement): the resident assignments against
+        the label columns of `extra`."""
+        return _partition_agreement([self], extra, nlogn, True)
+
+    def coassign_resident(self, rows, other=None):
+        """coassign_resident_many on this engine alone
+        (dist_gibbs_coassign_resident): 1.0 where the two resident rows share
+        a group, else 0.0."""
+        return _core.coassign_resident_many([self.core], rows, other, True)
+
+    def coassign_resident_torch(self, rows, other=None):
+        """coassign_resident for device index tensors -> a tensor"""
+        return _coassign_resident_torch([self], rows, other, True)
+
     def coassign_topk(self, values, other=None, k=10, exclude_self=None):
         """coassign_topk_many on this engine alone
         (dist_gibbs_coassign_topk) -> (index int32 [n, k], prob [n, k])"""
@@ -590,6 +606,228 @@ def coassign_many_torch(engines, values, other=None):
     feature) -> a [n, n_other] tensor on the same device; nothing is staged
     through the host."""
     return _coassign_torch(engines, values, other, False)
+
+
+# -- resident rows: what M chains say about the rows they hold ---------------
+class PartitionAgreement(object):
+    """What the device computes about P partitions of the same n rows, the
+    first m of them engines' resident assignments: sq[a, b] = the sum of the
+    squared cells of the contingency table of a and b (uint64 [P, P]) and
+    nlogn[a, b] = the sum of n log n over its cells (float64 [P, P], or
+    None).  The measures below are host arithmetic on the two."""
+
+    def __init__(self, sq, nlogn, n, m):
+        self.sq = sq
+        self.nlogn = nlogn
+        self.n = int(n)
+        self.m = int(m)
+
+    def __getitem__(self, key):
+        return getattr(self, key)
+
+
+def _is_tensor(c):
+    return hasattr(c, "data_ptr")
+
+
+def _label_bounds(columns, n_labels):
+    """n_labels per column; None: max + 1"""
+    if n_labels is not None:
+        if np.ndim(n_labels) == 0:
+            n_labels = [n_labels] * len(columns)
+        return [int(k) for k in n_labels]
+    return [(int(c.max()) + 1 if len(c) else 0) for c in columns]
+
+
+def _partition_agreement(engines, extra, nlogn, single, n_labels=None):
+    extra = [] if extra is None else list(extra)
+    if not engines and not extra:
+        raise RuntimeError("partition_agreement: no partition")
+    if any(g is None for g in engines):
+        raise RuntimeError("null engine")
+    dev = bool(extra) and all(_is_tensor(c) for c in extra)
+    if extra and not dev and any(_is_tensor(c) for c in extra):
+        raise RuntimeError("partition_agreement: label columns either all "
+                           "host arrays or all CUDA tensors")
+    if dev:
+        import torch
+        cols = []
+        for c in extra:
+            if not c.is_cuda or c.device != extra[0].device:
+                raise RuntimeError("label columns on one CUDA device")
+            if c.is_floating_point() or c.is_complex() or (
+                    c.dtype == torch.bool):
+                raise RuntimeError("label columns of integers")
+            if c.numel() and c.element_size() != 4 and (
+                    int(c.min()) < 0 or int(c.max()) > 0xFFFFFFFF):
+                raise RuntimeError("partition_agreement: label outside 32 "
+                                   "bits")
+            if c.element_size() != 4:
+                c = c.to(torch.int32)
+            cols.append(c.contiguous().reshape(-1))
+        bounds = _label_bounds(cols, n_labels)
+        lengths = [int(c.numel()) for c in cols]
+        # (the library works on its own stream: what filled the tensors on
+        # torch's must be done)
+        torch.cuda.current_stream(cols[0].device).synchronize()
+        handles = [int(c.data_ptr()) for c in cols]
+    else:
+        cols = [np.asarray(c).reshape(-1) for c in extra]
+        for c in cols:
+            if c.size and (c.min() < 0 or c.max() > 0xFFFFFFFF):
+                raise RuntimeError("partition_agreement: label outside 32 "
+                                   "bits")
+        bounds = _label_bounds(cols, n_labels)
+        lengths = [int(c.size) for c in cols]
+        handles = cols
+    n = engines[0].core.row_count() if engines else lengths[0]
+    for a, length in enumerate(lengths):
+        if length != n:
+            raise RuntimeError(
+                "partition_agreement: extra column %d has %d rows, not %d"
+                % (a, length, n))
+    if len(bounds) != len(cols):
+        raise RuntimeError("partition_agreement: one n_labels per column")
+    sq, nl = _core.partition_agreement_many(
+        [g.core for g in engines], n, handles, bounds, nlogn, dev, single)
+    return PartitionAgreement(sq, nl, n, len(engines))
+
+
+def partition_agreement_many(engines, extra=None, nlogn=True):
+    """Have the chains mixed, and which clustering do I report: the agreement
+    of the RESIDENT partitions of M engines -- `Gibbs` objects that hold the
+    same rows in the same order, which the caller vouches for -- and of the
+    label columns of `extra` (a ground truth, an earlier `assignments()`;
+    host arrays or CUDA tensors, bins up to max + 1).  -> a
+    `PartitionAgreement` over the P = M + len(extra) partitions, engines
+    first: sq exact, nlogn (None with nlogn=False) equal in every bit between
+    equal calls.  `rand_index`, `adjusted_rand_index`, `binder_distance`,
+    `variation_of_information` and `consensus` read it.  The engines are read
+    as `assignments()` reads them and nothing in them changes; a partition
+    may have at most 18 432 groups."""
+    return _partition_agreement(list(engines), extra, nlogn, False)
+
+
+def partition_agreement_labels(labels, n_labels=None, nlogn=True):
+    """partition_agreement_many for plain label columns and no engine
+    (dist_partition_agreement[_dev]): numpy arrays or CUDA tensors of one
+    length; n_labels: an exclusive bound per column (default max + 1)."""
+    return _partition_agreement([], labels, nlogn, False, n_labels)
+
+
+def _pair_counts(res):
+    """(T_ab, T_a as a column, C) in float64 from exact integers: the row
+    pairs joined by both partitions, by one, and all"""
+    sq = np.asarray(res.sq, np.uint64)
+    n = int(res.n)
+    t = ((sq - np.uint64(n)) // np.uint64(2)).astype(np.float64)
+    return t, np.diag(t).copy(), n * (n - 1) / 2.0
+
+
+def rand_index(res):
+    """-> float64 [P, P]: (C - T_a - T_b + 2 T_ab) / C; 1.0 for n < 2"""
+    t, ta, c = _pair_counts(res)
+    if c == 0:
+        return np.ones_like(t)
+    return (c - ta[:, None] - ta[None, :] + 2.0 * t) / c
+
+
+def adjusted_rand_index(res):
+    """-> float64 [P, P]: (T_ab - E) / ((T_a + T_b) / 2 - E) with
+    E = T_a T_b / C (Hubert and Arabie 1985); 1.0 where the denominator is 0
+    or n < 2"""
+    t, ta, c = _pair_counts(res)
+    if c == 0:
+        return np.ones_like(t)
+    e = ta[:, None] * ta[None, :] / c
+    den = (ta[:, None] + ta[None, :]) / 2.0 - e
+    out = np.ones_like(t)
+    np.divide(t - e, den, out=out, where=den != 0)
+    return out
+
+
+def binder_distance(res):
+    """-> int64 [P, P]: sq_aa + sq_bb - 2 sq_ab, the ordered row pairs that
+    one partition joins and the other separates"""
+    sq = np.asarray(res.sq, np.uint64).astype(np.int64)
+    d = np.diag(sq)
+    return d[:, None] + d[None, :] - 2 * sq
+
+
+def variation_of_information(res):
+    """-> float64 [P, P]: (nlogn_aa + nlogn_bb - 2 nlogn_ab) / n, in nats"""
+    if res.nlogn is None:
+        raise RuntimeError("variation_of_information: the result was "
+                           "computed with nlogn=False")
+    nl = np.asarray(res.nlogn, np.float64)
+    d = np.diag(nl)
+    return (d[:, None] + d[None, :] - 2.0 * nl) / float(res.n)
+
+
+def consensus(res, among=None):
+    """The least-squares clustering (Dahl 2006) -> (index, total_distance):
+    the member a of `among` (default: the m engines) with the smallest
+    sum over b in `among` of binder_distance[a, b] -- the sample nearest to
+    the posterior similarity matrix of those samples, which is never formed
+    --, the first minimum on ties; total_distance[i] is the sum of
+    among[i]."""
+    among = (np.arange(res.m) if among is None
+             else np.asarray(among, np.int64).reshape(-1))
+    if among.size == 0:
+        raise RuntimeError("consensus: no partition to choose among")
+    d = binder_distance(res)[np.ix_(among, among)]
+    total = d.sum(axis=1)
+    return int(among[int(np.argmin(total))]), total
+
+
+def coassign_resident_many(engines, rows, other=None):
+    """The posterior similarity of chosen RESIDENT rows -> float32
+    [len(rows), len(other)]: the fraction of `engines` in which rows[i] and
+    other[j] (None: rows) carry the same group id; with other=None symmetric
+    in every bit with a diagonal of 1.  The engines hold the same rows in the
+    same order; nothing in them changes."""
+    return _core.coassign_resident_many(_cores(engines), rows, other)
+
+
+def _device_rows(t, dev=None):
+    import torch
+    if not t.is_cuda or (dev is not None and t.device != dev):
+        raise RuntimeError("row indices on one CUDA device")
+    if t.is_floating_point() or t.dtype == torch.bool:
+        raise RuntimeError("row indices of integers")
+    t = t.reshape(-1)
+    # (4-byte words are read as unsigned: a negative int32 is out of range
+    # for the library as well)
+    if t.element_size() != 4:
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= 2 ** 31):
+            raise RuntimeError("coassign_resident_many: row index outside "
+                               "the engines' rows")
+        t = t.to(torch.int32)
+    return t.contiguous()
+
+
+def _coassign_resident_torch(engines, rows, other, single):
+    import torch
+    ra = _device_rows(rows)
+    dev = ra.device
+    rb = None if other is None else _device_rows(other, dev)
+    na = int(ra.numel())
+    nb = na if rb is None else int(rb.numel())
+    out = torch.empty((na, nb), dtype=torch.float32, device=dev)
+    # (the library works on its own stream: what filled the tensors on
+    # torch's must be done)
+    torch.cuda.current_stream(dev).synchronize()
+    _core.coassign_resident_many_dev(
+        _cores(engines), int(ra.data_ptr()), na,
+        0 if rb is None else int(rb.data_ptr()), nb, int(out.data_ptr()), nb,
+        single)
+    return out
+
+
+def coassign_resident_many_torch(engines, rows, other=None):
+    """coassign_resident_many for device index tensors -> a [n, n_other]
+    tensor on the same device; nothing is staged through the host."""
+    return _coassign_resident_torch(engines, rows, other, False)
 
 
 def _coassign_topk_flags(other, exclude_self):

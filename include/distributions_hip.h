@@ -1146,6 +1146,96 @@ int dist_gibbs_relate_many(dist_gibbs_t * const * engines, size_t m,
                            double * mi_out, double * stderr_out,
                            double * moments_out);
 
+/* What M chains say about their RESIDENT rows: the agreement of P partitions
+ * of the same n_rows rows, and the co-assignment of chosen resident rows.  An
+ * extension: the reference has no such member.
+ * The first m partitions are the resident assignments of m engines -- row i of
+ * every engine is the same datum, which the caller vouches for --, the other x
+ * are caller-supplied label columns (a ground truth, an earlier
+ * dist_gibbs_assignments).  For partitions a, b let
+ *   n_gh = #{i : label_a[i] = g and label_b[i] = h}.
+ * On the device, and nothing else:
+ *   sq[a * P + b] = sum_{g,h} n_gh^2: uint64, both triangles written, the
+ *     diagonal sum_g n_g^2.  Integers: exact in any order.
+ *   nlogn[a * P + b] = sum_{g,h : n_gh > 0} n_gh * log(n_gh): binary64 with the
+ *     platform's log, same shape.  NULL skips all of its work.  No
+ *     floating-point atomics: a cell is taken once, by its first row in the
+ *     stable order by a's label, partials are added in a fixed order, so equal
+ *     calls give equal bits.
+ * Rand and adjusted Rand indices, Binder's distance, the variation of
+ * information and the least-squares (Dahl 2006) consensus among the m samples
+ * are host arithmetic on these two matrices (the Python package has them).
+ * dist_partition_agreement_dev: labels_dev a HOST array of p DEVICE pointers
+ * to n_rows words each, n_labels[a] an exclusive bound on partition a's
+ * labels, sq_out / nlogn_out HOST arrays of p * p entries.  No engine is
+ * involved; it needs only a HIP device.  dist_partition_agreement stages host
+ * columns, calls and downloads.
+ * dist_gibbs_partition_agreement_many: partitions 0 .. m - 1 are the engines'
+ * assignments, then the x extra columns of n_rows words.  The engines are read
+ * under dist_gibbs_assignments' rules: a run a sweep left open stays
+ * resumable, value-sorted batches' assignments are flushed to row order, an
+ * open batch is refused.  Their labels -- global group ids, which grow without
+ * bound over a run -- are translated to packed indices on the device, so that
+ * an engine's bins are its dist_gibbs_group_count.
+ * dist_gibbs_partition_agreement is the m == 1 form.
+ * Bin limit: a partition may have at most 18 432 labels (n_labels, or an
+ * engine's group count): one uint32 count and one uint32 first-row word per
+ * label in 144 KiB of LDS.
+ * dist_gibbs_coassign_resident_many: out[i * ld + j] = float(c) / float(m), c
+ * the number of engines in which resident rows rows_a[i] and rows_b[j] carry
+ * the same group id (ld >= nb): the posterior similarity of chosen resident
+ * rows.  rows_b == NULL: rows_a, nb is ignored, the result is its own
+ * transpose and its diagonal 1.  dist_gibbs_coassign_resident: m == 1.
+ * Refused, before any launch unless noted: engines of unequal
+ * dist_gibbs_row_count, or n_rows that differs from it; an engine with
+ * unassigned rows (dist_gibbs_load_rows_unassigned not yet initialised
+ * through), naming the engine; the same engine twice; n_labels[a] above the
+ * bin limit, naming the partition; n_rows >= 2^31 (a row index travels through
+ * the sort doubled); a row index >= the engines' row count in rows_a / rows_b
+ * (the _dev form finds it by a kernel, which reads nothing there); a label >=
+ * n_labels[a] -- found by the first kernel, before anything reads a label as
+ * an index: the call fails naming the partition and the first such row, and
+ * the outputs are not written.  p == 0, m + x == 0 or n_rows == 0 does
+ * nothing.  Scratch is allocated per call: the order of the rows (n_rows
+ * words), one translated column, the sort's counters, p * p results.  Two
+ * host waits per agreement call, one per co-assignment call.
+ * _dev: label columns, row indices and out are device pointers (the arrays of
+ * pointers, n_labels, sq_out and nlogn_out stay host arrays). */
+int dist_partition_agreement_dev(size_t n_rows, size_t p,
+                                 const uint32_t * const * labels_dev,
+                                 const uint32_t * n_labels, uint64_t * sq_out,
+                                 double * nlogn_out);
+int dist_partition_agreement(size_t n_rows, size_t p,
+                             const uint32_t * const * labels,
+                             const uint32_t * n_labels, uint64_t * sq_out,
+                             double * nlogn_out);
+int dist_gibbs_partition_agreement_many_dev(
+    dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+    const uint32_t * const * extra_labels_dev, size_t x,
+    const uint32_t * extra_n_labels, uint64_t * sq_out, double * nlogn_out);
+int dist_gibbs_partition_agreement_many(
+    dist_gibbs_t * const * engines, size_t m, size_t n_rows,
+    const uint32_t * const * extra_labels, size_t x,
+    const uint32_t * extra_n_labels, uint64_t * sq_out, double * nlogn_out);
+int dist_gibbs_partition_agreement(dist_gibbs_t * g, size_t n_rows,
+                                   const uint32_t * const * extra_labels,
+                                   size_t x, const uint32_t * extra_n_labels,
+                                   uint64_t * sq_out, double * nlogn_out);
+int dist_gibbs_coassign_resident_many_dev(
+    dist_gibbs_t * const * engines, size_t m, const uint32_t * rows_a_dev,
+    size_t na, const uint32_t * rows_b_dev, size_t nb, float * out_dev,
+    size_t ld);
+int dist_gibbs_coassign_resident_many(
+    dist_gibbs_t * const * engines, size_t m, const uint32_t * rows_a,
+    size_t na, const uint32_t * rows_b, size_t nb, float * out, size_t ld);
+int dist_gibbs_coassign_resident_dev(dist_gibbs_t * g,
+                                     const uint32_t * rows_a_dev, size_t na,
+                                     const uint32_t * rows_b_dev, size_t nb,
+                                     float * out_dev, size_t ld);
+int dist_gibbs_coassign_resident(dist_gibbs_t * g, const uint32_t * rows_a,
+                                 size_t na, const uint32_t * rows_b, size_t nb,
+                                 float * out, size_t ld);
+
 size_t dist_gibbs_group_count(const dist_gibbs_t * g);     /* counts().size() */
 size_t dist_gibbs_row_count(const dist_gibbs_t * g);
 int dist_gibbs_counts(const dist_gibbs_t * g, int * out);  /* driver counts() */
