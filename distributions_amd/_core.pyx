@@ -391,6 +391,7 @@ cdef extern from "distributions_hip.h" nogil:
     int dist_gibbs_kernel_stats(dist_gibbs_t *, double *, uint64_t *,
                                 uint64_t *, int)
     int dist_gibbs_set_option(dist_gibbs_t *, const char *, int)
+    int dist_gibbs_set_certified_search(dist_gibbs_t *, int, int)
     int dist_gibbs_path_counts(const dist_gibbs_t *, uint64_t *, uint64_t *)
     int dist_gibbs_shared(const dist_gibbs_t *, int, dist_shared_t *)
     int dist_gibbs_clustering(const dist_gibbs_t *, float *, float *)
@@ -1819,8 +1820,8 @@ cdef class GibbsEngine:
 
     def debug_counts(self):
         """dict of the engine's path diagnostics (dist_gibbs_debug_counts)"""
-        cdef uint64_t out[18]
-        check(dist_gibbs_debug_counts(self.ptr, out, 18))
+        cdef uint64_t out[21]
+        check(dist_gibbs_debug_counts(self.ptr, out, 21))
         return {"value_sorted_batches": out[0], "other_batches": out[1],
                 "band_launches": out[2], "running_sum_launches": out[3],
                 "band_values_last": out[4], "handed_over_last": out[5],
@@ -1829,7 +1830,9 @@ cdef class GibbsEngine:
                 "fold_batches": out[10], "scan_batches": out[11],
                 "merged_batches": out[12], "fused_batches": out[13],
                 "resumed_runs": out[14], "chain_launches": out[15],
-                "rows_folded_last": out[16], "rows_instance_last": out[17]}
+                "rows_folded_last": out[16], "rows_instance_last": out[17],
+                "search_batches": out[18], "rows_certified": out[19],
+                "rows_left_over": out[20]}
 
     def chain_launches(self):
         """launches of the exact-chain kernel this engine issued"""
@@ -1837,6 +1840,11 @@ cdef class GibbsEngine:
 
     def set_option(self, name, int value):
         check(dist_gibbs_set_option(self.ptr, name.encode(), value))
+
+    def set_certified_search(self, int mode, int slack=0):
+        """k_vs_search in k_vs_sample's place: 0 never, 1 auto, 2 wherever it
+        applies; the certificate's bound times 2^slack (tests)"""
+        check(dist_gibbs_set_certified_search(self.ptr, mode, slack))
 
     def path_counts(self):
         """-> (batches served by the value-sorted kernel, by the generic one)"""

@@ -1275,6 +1275,15 @@ struct Gibbs {
         // where the running sums would be built (default), 2 whenever
         // k_vs_tables runs
         int shared_totals_mode = 1;
+        // k_vs_search in k_vs_sample's place (kernels_vs.h: a certified
+        // prefix-sum search per row, the exact chain for the rows it leaves
+        // over):
+        // 0 never, 1 where it applies and pays (default), 2 wherever it
+        // applies -- a fused batch with shared totals whose search tables fit
+        // the LDS.  certify_slack scales the certificate's bound by 2^slack
+        // (tests: small shapes reach the leftover path; 200 certifies nothing)
+        int certified_search_mode = 1;
+        int certify_slack = 0;
         // k_score_rows takes one work-item per (row, group): a launch covers
         // at most this many, whole rows each (default 2^30, under the 2^32 of
         // a 1-D grid)
@@ -1413,6 +1422,11 @@ struct Gibbs {
     std::vector<std::pair<size_t, size_t>> vs_ranges;   // [r0, r1) of each
     size_t vs_last = 0;   // where the last look-up found its range
     DeviceBuf<float> vsLA, vsLB, vsM, vsmB, vsPA, vsPB, vsOwn, vsTot;
+    // k_vs_search: the rows it leaves to its chain phase (VsLeft) and its
+    // row counters, a pair per workgroup slot
+    DeviceBuf<VsLeftRow> vsLeftRows;
+    DeviceBuf<unsigned long long> vsLeftStats;
+    uint64_t search_batches = 0;
     DeviceBuf<int> remap_log;   // the batches' swap-removals (kernels.h)
     DeviceBuf<int32_t> vs_stage;   // [chunks][K] deltas of the open batch
     DeviceBuf<int> vsBandMode;     // VsTables::band_mode
@@ -3206,6 +3220,7 @@ struct Gibbs {
         VsTables T;
         bool narrow;
         bool fused;
+        VsLeft left;   // (rows set: k_vs_search in k_vs_sample's place)
         template <int KIND>
         void go() {
             const uint32_t nv = (uint32_t)self->vs_nvals();
@@ -3256,6 +3271,17 @@ struct Gibbs {
                 else
                     launch(std::integral_constant<int, 4>());
                 HIP_CHECK(hipGetLastError());
+                self->tm.mark(self->tm.ev1);
+                return;
+            }
+            // the certified search takes every row of the tables' chunks,
+            // the rows it cannot certify through the chain included
+            if (left.rows) {
+                if (c->n_tiles)
+                    launch_lds<&k_vs_search>(
+                        dim3(c->n_table_chunks), dim3(kVsSearchBlock),
+                        vs_search_lds(T.Kuse), *P, T, c->chunks.p,
+                        c->n_table_chunks, c->sorted_rows.p, D, left);
                 self->tm.mark(self->tm.ev1);
                 return;
             }
@@ -3568,6 +3594,19 @@ struct Gibbs {
             vsPA.reserve(grow_capacity((size_t)nv * (Kpad / kVsUnroll)), 0);
             vsPB.reserve(grow_capacity((size_t)nv * (Kpad / kVsUnroll)), 0);
         }
+        // the certified search: where the cells' totals are built (a fused
+        // batch: chunks of one value each), the tiles are the wide ones and
+        // the search tables fit the LDS.  Auto: where, besides, every chunk's
+        // workgroup is resident at once -- k_vs_search's workgroups take a
+        // CU each, and a second round of them costs more than the chain
+        // saves (Zipf values, some 400 chunks, 56 against 52 us);
+        // it won at every group count whose tables fit
+        const bool search = totals && !narrow && opt.certified_search_mode != 0
+                            && c.one_value_chunks && c.n_table_chunks != 0
+                            && Kpad <= kVsCertifyMaxK
+                            && vs_search_lds(Kuse) <= kLdsWorkgroupLimit
+                            && (opt.certified_search_mode == 2
+                                || c.n_table_chunks <= (uint32_t)cu_count());
         if (fused) vsOwn.reserve(grow_capacity((size_t)nv * Kpad), 0);
         if (totals) vsTot.reserve(grow_capacity((size_t)nv * Kpad), 0);
         deferred.reserve(std::max<size_t>(n, 1), 0);
@@ -3584,7 +3623,18 @@ struct Gibbs {
         }
         P.sorted_rows = c.sorted_rows.p;
         P.assign_pos = c.assign_pos.p;
-        VsLaunch L{this, &P, &c, {}, narrow, fused};
+        VsLaunch L{this, &P, &c, {}, narrow, fused, {}};
+        memset(&L.left, 0, sizeof(L.left));
+        if (search) {
+            vsLeftRows.reserve(std::max<size_t>(n, 1), 0);
+            // (zeros; what the slots have counted so far is kept)
+            vsLeftStats.reserve(grow_capacity(2 * (size_t)c.n_chunks),
+                                vsLeftStats.cap);
+            L.left.rows = vsLeftRows.p;
+            L.left.stats = vsLeftStats.p;
+            L.left.slack = opt.certify_slack;
+            search_batches += 1;
+        }
         VsTables & T = L.T;
         memset(&T, 0, sizeof(T));
         T.LA = vsLA.p;
@@ -9844,6 +9894,15 @@ int dist_gibbs_set_option(dist_gibbs_t * g, const char * name, int value) {
         if (o->drops_ranges) e.drop_overlapping_caches(0, e.n_rows, false);
     });
 }
+int dist_gibbs_set_certified_search(dist_gibbs_t * g, int mode, int slack) {
+    return guarded([&] {
+        DIST_REQUIRE(mode >= 0 && mode <= 2, "certified_search: 0, 1 or 2");
+        DIST_REQUIRE(slack >= 0 && slack <= 200, "certify_slack: 0 to 200");
+        Gibbs & e = *g->impl;   // (settles an open run)
+        e.opt.certified_search_mode = mode;
+        e.opt.certify_slack = slack;
+    });
+}
 int dist_gibbs_path_counts(const dist_gibbs_t * g, uint64_t * value_sorted,
                            uint64_t * generic) {
     return guarded([&] {
@@ -9854,13 +9913,19 @@ int dist_gibbs_path_counts(const dist_gibbs_t * g, uint64_t * value_sorted,
 int dist_gibbs_debug_counts(dist_gibbs_t * g, uint64_t * out, size_t n) {
     return guarded([&] {
         Gibbs & e = *g->impl.read();
-        uint64_t v[18] = {e.vs_batches, e.generic_batches, e.band_batches,
+        uint64_t v[21] = {e.vs_batches, e.generic_batches, e.band_batches,
                           e.prefix_batches, 0, 0, e.stream_batches,
                           e.run.async_batches, e.narrow_batches,
                           e.scratch_batches, e.fold_batches, e.scan_batches,
                           e.merged_batches, e.fused_batches, e.run.resumed_runs,
                           e.chain_launches, e.rows_folded_last,
-                          e.rows_instance_last};
+                          e.rows_instance_last, e.search_batches, 0, 0};
+        if (e.vsLeftStats.p) {
+            // rows the certified search answered itself / left to the chain
+            std::vector<unsigned long long> rows(e.vsLeftStats.cap);
+            e.vsLeftStats.download(rows.data(), rows.size());
+            for (size_t i = 0; i < rows.size(); ++i) v[19 + (i & 1)] += rows[i];
+        }
         if (e.last_bands && !e.batch_open && e.vsBandMode.p) {
             // values whose arg-max group's rows had a tile of their own in
             // the last value-sorted launch
@@ -9876,7 +9941,7 @@ int dist_gibbs_debug_counts(dist_gibbs_t * g, uint64_t * out, size_t n) {
             e.deferred_count.download(&d, 1);
             v[5] = d;
         }
-        for (size_t i = 0; i < n && i < 18; ++i) out[i] = v[i];
+        for (size_t i = 0; i < n && i < 21; ++i) out[i] = v[i];
     });
 }
 int dist_gibbs_phase_stats(dist_gibbs_t * g, double ms_out[5],

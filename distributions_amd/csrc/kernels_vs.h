@@ -2,6 +2,7 @@
 // value tables (k_vs_prepare / k_vs_tables), k_vs_sample, k_vs_narrow,
 // k_vs_stream, the scan-sampling variants.  Part of kernels.h.
 #pragma once
+#include "vs_certify.h"
 
 namespace dist {
 
@@ -75,6 +76,24 @@ __device__ __forceinline__ void vs_hand_over(const VsDefer & D, uint32_t chunk,
     else
         D.list[atomicAdd(D.count, 1u)] = at;
 }
+// A row k_vs_search could not certify (vs_certify.h), as its workgroup's
+// chain phase needs it: the chunk's stretch of `rows` (positions
+// chunks[c].pos ...) takes the rows of the value's other groups from the
+// front and the arg-max group's from the back.
+struct __attribute__((aligned(16))) VsLeftRow {
+    uint32_t at;     // position in the sorted row list
+    int g;           // own slot
+    float l_own;     // its entry with the row taken out
+    float t0;        // fl(total * u): where the chain starts
+};
+static_assert(sizeof(VsLeftRow) == 16, "one 16-byte record per row");
+struct VsLeft {
+    VsLeftRow * rows;                // null: no search in this launch
+    // [n_chunks][2] rows certified / rows left to the chain, summed over the
+    // launches per workgroup slot (each slot has one writer per launch)
+    unsigned long long * stats;
+    int slack;                       // the bound times 2^slack (tests)
+};
 struct VsTables {
     float * LA;      // [nvals][Kpad]
     float * LB;
@@ -1511,6 +1530,298 @@ void k_vs_sample(
                | ((unsigned long long)chunks_done << 40);
     }
 #endif
+}
+
+// ---------------------------------------------------------------------------
+// The certified search (option "certified_search"; exact).  k_vs_sample's
+// chain answers, per row, "the first k at which t0 minus the entries so far
+// is no longer positive".  The entries are the VALUE's but for the own slot,
+// so a float64 prefix sum per value answers it for all its rows by binary
+// search -- log2 K dependent LDS reads instead of K dependent adds -- and the
+// bound of vs_certify.h tells for which rows that answer is provably the
+// chain's.  The others, a few per cent, run the chain itself, in the same
+// workgroup and from the same LDS copy of the vector.
+//
+// One workgroup per apply chunk (one value, <= kVsApplyRows rows), in place of
+// k_vs_sample's launch.  It requests its rows' set-up words (k_vs_sample's
+// stages, kVsSearchRows rows per thread), builds in LDS, for LA[x] and LB[x]
+// each, the floats, their float64 inclusive prefix sums C and the prefix sums
+// D of C (the tight bound's sum of the t_i) by a blocked scan of fixed shape
+// -- thread i owns entries [i P, (i + 1) P) -- and searches.  Rows with
+// own < 0 are handed over as the tiles hand them over.  Then its waves take
+// the rows that are left, 64 of one class per wave, through the float chain:
+// one row per lane, the entries broadcast from LDS, the early exit and the
+// replay of the crossing chunk as in vs_sum_and_scan -- the same
+// subtractions in the same order.  Nothing waits on another workgroup.  The
+// kernel is the same for every kind: what depends on the kind is in the
+// tables.
+constexpr int kVsSearchBlock = 1024;
+constexpr int kVsSearchRows = kVsApplyRows / kVsSearchBlock;
+static_assert(kVsApplyRows % kVsSearchBlock == 0, "rows per thread");
+// floats, C and D of both vectors
+constexpr size_t vs_search_lds(int Kuse) { return (size_t)Kuse * 40; }
+// exclusive offsets of a pair of per-thread sums over the workgroup, thread
+// order (wave scans, then the waves' totals through `ws`, [2][waves] doubles)
+__device__ __forceinline__ void vs_search_offsets(double & a, double & b,
+                                                  double * ws) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double ia = a, ib = b;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double ua = __shfl_up(ia, off), ub = __shfl_up(ib, off);
+        if (lane >= off) { ia += ua; ib += ub; }
+    }
+    __syncthreads();   // (ws may still be read from the last call)
+    if (lane == 63) {
+        ws[wave] = ia;
+        ws[kVsSearchBlock / 64 + wave] = ib;
+    }
+    __syncthreads();
+    double oa = 0.0, ob = 0.0;
+    for (int w = 0; w < wave; ++w) {
+        oa += ws[w];
+        ob += ws[kVsSearchBlock / 64 + w];
+    }
+    // (sums of non-negative terms only: nothing is subtracted back out)
+    const double ea = __shfl_up(ia, 1), eb = __shfl_up(ib, 1);
+    a = lane ? oa + ea : oa;
+    b = lane ? ob + eb : ob;
+}
+// The chain of one row per lane over the vector L in LDS (entries at and past
+// K are zero): t = fl(t - e_k), the own slot's entry replaced by l_own; the
+// first k with t <= 0, at most K - 1.  As in vs_sum_and_scan the loop only
+// counts the chunks that end with t > 0 and keeps the last such t, and the
+// lane replays its crossing chunk.
+// one chunk of the chain: t through entries k0 .. k0 + 31 (v: the chunk)
+__device__ __forceinline__ void vs_left_chunk(
+        float & t, const float4 (&v)[kVsUnroll / 4], int k0, int g,
+        int gpiece, float l_own) {
+#pragma unroll
+    for (int b = 0; b < kVsUnroll / 8; ++b) {
+        const float e[8] = {v[2 * b].x, v[2 * b].y, v[2 * b].z, v[2 * b].w,
+                            v[2 * b + 1].x, v[2 * b + 1].y, v[2 * b + 1].z,
+                            v[2 * b + 1].w};
+        // (only the eight-entry pieces that hold an own slot select)
+        if (__builtin_amdgcn_ballot_w64(gpiece == (k0 >> 3) + b) != 0) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                t -= (k0 + 8 * b + j == g) ? l_own : e[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) t -= e[j];
+        }
+    }
+}
+__device__ __forceinline__ void vs_left_fetch(
+        float4 (&v)[kVsUnroll / 4], const float * L, int k0) {
+#pragma unroll
+    for (int q = 0; q < kVsUnroll / 4; ++q)
+        v[q] = reinterpret_cast<const float4 *>(L + k0)[q];
+}
+__device__ __forceinline__ int vs_left_chain(const float * L, int K, int g,
+                                             float l_own, float t,
+                                             bool active) {
+    const int nchunks = (K + kVsUnroll - 1) / kVsUnroll;
+    const int last = (nchunks - 1) * kVsUnroll;
+    const int gpiece = active ? (g >> 3) : -1;
+    float t_start = t;
+    int npos = 0;
+    // (a wave runs this alone on its SIMD: the next chunk is read while this
+    // one is subtracted, two chunks a trip; `last` keeps the read ahead
+    // inside the vector)
+    float4 va[kVsUnroll / 4], vb[kVsUnroll / 4];
+    vs_left_fetch(va, L, 0);
+    for (int k0 = 0; k0 < K; k0 += 2 * kVsUnroll) {
+        vs_left_fetch(vb, L, min(k0 + kVsUnroll, last));
+        vs_left_chunk(t, va, k0, g, gpiece, l_own);
+        bool pos = t > 0.f;
+        t_start = pos ? t : t_start;
+        npos += pos ? 1 : 0;
+        if (__builtin_amdgcn_ballot_w64(active && pos) == 0
+            || k0 + kVsUnroll >= K)
+            break;
+        vs_left_fetch(va, L, min(k0 + 2 * kVsUnroll, last));
+        vs_left_chunk(t, vb, k0 + kVsUnroll, g, gpiece, l_own);
+        pos = t > 0.f;
+        t_start = pos ? t : t_start;
+        npos += pos ? 1 : 0;
+        if (__builtin_amdgcn_ballot_w64(active && pos) == 0) break;
+    }
+    int f = K - 1;
+    if (active && npos < nchunks) {
+        const float * chunk = L + npos * kVsUnroll;
+        const int own = g - npos * kVsUnroll;   // in 0..31 or not
+        float tt = t_start;
+        int steps = 0;
+#pragma unroll
+        for (int j = 0; j < kVsUnroll; ++j) {
+            tt -= (own == j) ? l_own : chunk[j];
+            steps += (tt > 0.f) ? 1 : 0;
+        }
+        f = npos * kVsUnroll + steps;
+    }
+    return f < K - 1 ? f : K - 1;
+}
+__global__ __launch_bounds__(kVsSearchBlock) void k_vs_search(
+        SweepParams P, VsTables T, const VsTile * __restrict__ chunks,
+        uint32_t n_chunks, const uint32_t * __restrict__ sorted_rows,
+        VsDefer D, VsLeft Lf) {
+    extern __shared__ __attribute__((aligned(16))) double sr_lds[];
+    __shared__ double ws[2 * (kVsSearchBlock / 64)];
+    __shared__ uint32_t s_left[2], s_cert, s_emax;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t chunk = blockIdx.x;
+    if (chunk >= n_chunks) return;
+    const VsTile me = vs_load_tile(chunks + chunk);
+    const uint32_t x = me.x, pos = me.pos, n = me.n;
+    // (rows beyond the tables are k_vs_apply's)
+    if (x >= T.n_values || n == 0) return;
+    const int K = P.dev ? uniform_load(&P.dev->K) : P.K;
+    const int Kuse = T.Kuse;
+    double * CA = sr_lds, * DA = CA + Kuse, * CB = DA + Kuse,
+           * DB = CB + Kuse;
+    float * FA = reinterpret_cast<float *>(DB + Kuse), * FB = FA + Kuse;
+    if (threadIdx.x == 0) {
+        s_left[0] = s_left[1] = s_cert = 0;
+        s_emax = __float_as_uint(1.f);
+    }
+    // the rows' words: k_vs_sample's stages, kVsSearchRows rows of a thread
+    // at once and under the table build below; threads without a row load
+    // through the chunk's last one
+    bool valid[kVsSearchRows];
+    uint32_t at[kVsSearchRows], b[kVsSearchRows], chain[kVsSearchRows];
+    int g[kVsSearchRows];
+    RowDrawWords w[kVsSearchRows];
+    float l_own[kVsSearchRows], total[kVsSearchRows];
+#pragma unroll
+    for (int r = 0; r < kVsSearchRows; ++r) {
+        const uint32_t i = (uint32_t)r * kVsSearchBlock + threadIdx.x;
+        valid[r] = i < n;
+        at[r] = pos + (valid[r] ? i : n - 1);
+        b[r] = sorted_rows[at[r]];
+        chain[r] = P.assign_pos[at[r]];
+    }
+#pragma unroll
+    for (int r = 0; r < kVsSearchRows; ++r) {
+        g[r] = P.g2p[chain[r]];
+        w[r] = batch_row_draw_words(P, b[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < kVsSearchRows; ++r) {
+        l_own[r] = T.own[(size_t)x * T.Kpad + g[r]];
+        total[r] = T.tot[(size_t)x * T.Kpad + g[r]];
+    }
+    // the tables: entries at and past the group count are never asked for
+    // (the search stays below K) and count as zero
+    const int per = (Kuse + kVsSearchBlock - 1) / kVsSearchBlock;
+    const int k_lo = min((int)threadIdx.x * per, Kuse);
+    const int k_hi = min(k_lo + per, Kuse);
+    const float * la = T.LA + (size_t)x * T.Kpad,
+                * lb = T.LB + (size_t)x * T.Kpad;
+    double sa = 0.0, sb = 0.0;
+    float big = 0.f;
+    for (int k = k_lo; k < k_hi; ++k) {
+        const float ea = k < K ? la[k] : 0.f, eb = k < K ? lb[k] : 0.f;
+        FA[k] = ea;
+        FB[k] = eb;
+        sa += (double)ea;
+        sb += (double)eb;
+        big = fmaxf(big, fmaxf(ea, eb));
+    }
+    double oa = sa, ob = sb;
+    vs_search_offsets(oa, ob, ws);
+    // (non-negative floats order as their bit patterns)
+    if (!(big <= 1.f)) atomicMax(&s_emax, __float_as_uint(big));
+    double da = 0.0, db = 0.0;
+    for (int k = k_lo; k < k_hi; ++k) {
+        oa += (double)FA[k];
+        ob += (double)FB[k];
+        CA[k] = oa;
+        CB[k] = ob;
+        da += oa;
+        db += ob;
+    }
+    double pa = da, pb = db;
+    vs_search_offsets(pa, pb, ws);
+    for (int k = k_lo; k < k_hi; ++k) {
+        pa += CA[k];
+        pb += CB[k];
+        DA[k] = pa;
+        DB[k] = pb;
+    }
+    __syncthreads();
+    const float emax_f = __uint_as_float(s_emax);
+    int steps = 0;
+    while ((1 << steps) < K) ++steps;
+    const int amax = uniform_load(&T.argmax[x]);
+
+    // the search: a thread's rows take their steps side by side (rows that
+    // are not there or are handed over stand still at index 0)
+    bool live[kVsSearchRows], classB[kVsSearchRows];
+    float t0[kVsSearchRows];
+    double delta[kVsSearchRows];
+    int lo[kVsSearchRows], hi[kVsSearchRows];
+#pragma unroll
+    for (int r = 0; r < kVsSearchRows; ++r) {
+        live[r] = valid[r] && !(l_own[r] < 0.f);
+        if (valid[r] && !live[r]) vs_hand_over(D, chunk, at[r]);
+        // (the chain's own product: one float multiply)
+        t0[r] = live[r] ? total[r] * batch_row_draw_unif01(P, w[r]) : 0.f;
+        classB[r] = g[r] == amax;
+        delta[r] = (double)l_own[r] - (double)(classB[r] ? FB : FA)[g[r]];
+        lo[r] = 0;
+        hi[r] = vs_search_top(K, t0[r]);
+    }
+    for (int s = 0; s < steps; ++s) {
+#pragma unroll
+        for (int r = 0; r < kVsSearchRows; ++r)
+            vs_search_step(classB[r] ? CB : CA, g[r], delta[r],
+                           (double)t0[r], lo[r], hi[r]);
+    }
+    uint32_t n_cert = 0;
+    bool certified[kVsSearchRows];
+#pragma unroll
+    for (int r = 0; r < kVsSearchRows; ++r)
+        certified[r] = vs_certify_decide(
+            classB[r] ? CB : CA, classB[r] ? DB : DA, K, g[r], delta[r],
+            t0[r], (double)fmaxf(emax_f, l_own[r]), Lf.slack, lo[r]);
+#pragma unroll
+    for (int r = 0; r < kVsSearchRows; ++r) {
+        if (live[r] && certified[r]) {
+            P.old_packed[at[r]] = (uint32_t)g[r];
+            P.new_packed[at[r]] = (uint32_t)lo[r];
+            n_cert += 1;
+        } else if (live[r]) {
+            const uint32_t i = atomicAdd(&s_left[classB[r] ? 1 : 0], 1u);
+            Lf.rows[pos + (classB[r] ? n - 1 - i : i)] =
+                VsLeftRow{at[r], g[r], l_own[r], t0[r]};
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) n_cert += __shfl_xor(n_cert, off);
+    if (lane == 0 && n_cert) atomicAdd(&s_cert, n_cert);
+    __syncthreads();   // (the records are this workgroup's to read)
+    const uint32_t nA = s_left[0], nB = s_left[1];
+    if (threadIdx.x == 0) {
+        Lf.stats[2 * chunk] += s_cert;
+        Lf.stats[2 * chunk + 1] += nA + nB;
+    }
+    // the chain for what is left: 64 rows of one class per wave and trip
+    const uint32_t itemsA = (nA + 63) / 64, items = itemsA + (nB + 63) / 64;
+    for (uint32_t it = wave; it < items; it += kVsSearchBlock / 64) {
+        const bool isB = it >= itemsA;
+        const uint32_t first = isB ? (it - itemsA) * 64 : it * 64;
+        const uint32_t i = first + lane;
+        const bool active = i < (isB ? nB : nA);
+        const uint32_t slot = active ? i : first;   // (a row that is there)
+        const VsLeftRow row = Lf.rows[pos + (isB ? n - 1 - slot : slot)];
+        const int f = vs_left_chain(isB ? FB : FA, K, row.g, row.l_own,
+                                    row.t0, active);
+        if (active) {
+            P.old_packed[row.at] = (uint32_t)row.g;
+            P.new_packed[row.at] = (uint32_t)f;
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------

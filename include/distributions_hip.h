@@ -1394,10 +1394,20 @@ int dist_gibbs_sharded_device_normalise_ok(const dist_gibbs_t * g,
  *      or dist_gibbs_predict_feature launch takes (2^22)
  */
 int dist_gibbs_set_option(dist_gibbs_t * g, const char * name, int value);
+/* The certified search.  EXACT at every setting.  k_vs_search, in
+ * k_vs_sample's place, answers a row's inverse CDF by binary search on the
+ * value's float64 prefix sums where a bound on the float chain's rounding
+ * proves the index (csrc/vs_certify.h), and runs the chain itself on the rows
+ * that are left over.  mode: 0 never | 1 where the library chooses (default)
+ * | 2 wherever it applies (a fused batch with shared totals whose search
+ * tables fit the LDS).  slack in 0..200, for tests: the bound times 2^slack
+ * (default 0), so that small shapes leave rows to the chain; 200 certifies
+ * nothing.  tests/test_gpu_certified_search.py */
+int dist_gibbs_set_certified_search(dist_gibbs_t * g, int mode, int slack);
 /* how many batches each score+sample kernel has served */
 int dist_gibbs_path_counts(const dist_gibbs_t * g, uint64_t * value_sorted,
                            uint64_t * generic);
-/* diagnostics for the tests: out[0..17] = batches through the value-sorted
+/* diagnostics for the tests: out[0..20] = batches through the value-sorted
  * kernel, through the other kernels, launches with band tiles on, launches
  * with running sums on, values whose arg-max rows had their own tile in the
  * last value-sorted launch, rows that launch handed to the wave-per-row
@@ -1412,7 +1422,9 @@ int dist_gibbs_path_counts(const dist_gibbs_t * g, uint64_t * value_sorted,
  * per-(joint value, group) table, out[17] the instance that launch took by
  * the ops that remained (0 generic, 1 GN, 2 N, 3 NN, 4 G, 5 C; G a table
  * gather, C a categorical, N a NormalInverseChiSq); both 0 before any such
- * launch (first min(n, 18) entries are written) */
+ * launch; out[18] batches that took the certified search, out[19] the rows
+ * it answered itself and out[20] the rows it left to the chain, summed over
+ * those batches (first min(n, 21) entries are written) */
 int dist_gibbs_debug_counts(dist_gibbs_t * g, uint64_t * out, size_t n);
 /* "phase_timing" = 1 (a diagnostic: six events per sub-sweep): HIP-event time
  * (ms, summed) of the five phases of the device-normalised value-sorted
