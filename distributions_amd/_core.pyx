@@ -285,6 +285,30 @@ cdef extern from "distributions_hip.h" nogil:
     int dist_gibbs_coassign_resident(
         dist_gibbs_t *, const uint32_t *, size_t, const uint32_t *, size_t,
         float *, size_t) nogil
+    int dist_gibbs_search_resident_many_dev(
+        dist_gibbs_t * const *, size_t, size_t, const uint32_t * const *,
+        size_t, size_t, size_t, unsigned, uint32_t *, float *, size_t) nogil
+    int dist_gibbs_search_resident_many(
+        dist_gibbs_t * const *, size_t, size_t, const uint32_t * const *,
+        size_t, size_t, size_t, unsigned, uint32_t *, float *, size_t) nogil
+    int dist_gibbs_search_resident_dev(
+        dist_gibbs_t *, size_t, const uint32_t * const *, size_t, size_t,
+        size_t, unsigned, uint32_t *, float *, size_t) nogil
+    int dist_gibbs_search_resident(
+        dist_gibbs_t *, size_t, const uint32_t * const *, size_t, size_t,
+        size_t, unsigned, uint32_t *, float *, size_t) nogil
+    int dist_gibbs_coassign_resident_topk_many_dev(
+        dist_gibbs_t * const *, size_t, const uint32_t *, size_t, size_t,
+        size_t, size_t, unsigned, uint32_t *, float *, size_t) nogil
+    int dist_gibbs_coassign_resident_topk_many(
+        dist_gibbs_t * const *, size_t, const uint32_t *, size_t, size_t,
+        size_t, size_t, unsigned, uint32_t *, float *, size_t) nogil
+    int dist_gibbs_coassign_resident_topk_dev(
+        dist_gibbs_t *, const uint32_t *, size_t, size_t, size_t, size_t,
+        unsigned, uint32_t *, float *, size_t) nogil
+    int dist_gibbs_coassign_resident_topk(
+        dist_gibbs_t *, const uint32_t *, size_t, size_t, size_t, size_t,
+        unsigned, uint32_t *, float *, size_t) nogil
     int dist_gibbs_coassign_topk_many_dev(
         dist_gibbs_t * const *, size_t, size_t, const uint32_t * const *,
         size_t, const uint32_t * const *, size_t, unsigned, uint32_t *,
@@ -2626,6 +2650,163 @@ def coassign_topk_many(engines, values, other, size_t k, unsigned flags,
     free(ptrs)
     free(qc)
     free(tc)
+    check(rc)
+    return (np.ascontiguousarray(index[:, :k]),
+            np.ascontiguousarray(prob[:, :k]))
+
+
+def search_resident_many_dev(engines, q_ptrs, size_t n_q, size_t row_begin,
+                             size_t row_end, size_t k, unsigned flags,
+                             size_t index_ptr, size_t prob_ptr, size_t ld,
+                             bint single=False):
+    """Per held-out query the k most co-assigned RESIDENT rows of [row_begin,
+    row_end) over M engines (dist_gibbs_search_resident_many_dev; single:
+    dist_gibbs_search_resident_dev): q_ptrs as coassign_many_dev's, index_ptr
+    and prob_ptr the device addresses of [n_q, ld] uint32 words and floats."""
+    cdef size_t m = len(engines)
+    if single and m != 1:
+        raise RuntimeError("search_resident: one engine")
+    cdef GibbsEngine first
+    if m and engines[0] is not None:
+        first = engines[0]
+        if len(q_ptrs) != len(first.shareds):
+            raise RuntimeError("one value column per feature")
+    cdef const uint32_t ** qc = _address_columns(q_ptrs)
+    cdef dist_gibbs_t ** ptrs
+    cdef int rc
+    try:
+        ptrs = _engine_ptrs(engines)
+    except Exception:
+        free(qc)
+        raise
+    with nogil:
+        if single:
+            rc = dist_gibbs_search_resident_dev(
+                ptrs[0], n_q, qc, row_begin, row_end, k, flags,
+                <uint32_t *> index_ptr, <float *> prob_ptr, ld)
+        else:
+            rc = dist_gibbs_search_resident_many_dev(
+                <dist_gibbs_t * const *> ptrs, m, n_q, qc, row_begin, row_end,
+                k, flags, <uint32_t *> index_ptr, <float *> prob_ptr, ld)
+    free(ptrs)
+    free(qc)
+    check(rc)
+
+
+def search_resident_many(engines, values, size_t row_begin, size_t row_end,
+                         size_t k, unsigned flags=0, bint single=False,
+                         ld=None):
+    """search_resident_many_dev from host arrays
+    (dist_gibbs_search_resident_many; single: dist_gibbs_search_resident);
+    ld: the row stride handed to the library (None: k).
+    -> (uint32 [n_q, k], float32 [n_q, k])"""
+    cdef size_t m = len(engines)
+    if single and m != 1:
+        raise RuntimeError("search_resident: one engine")
+    cdef GibbsEngine first
+    qw, rows_q = [], 0
+    if m and engines[0] is not None:
+        first = engines[0]
+        qw, rows_q = _word_columns(first, values)
+    cdef size_t nf = len(qw)
+    cdef size_t n_q = rows_q
+    cdef size_t stride = k if ld is None else ld
+    cdef size_t width = max(stride, k)
+    cdef cnp.ndarray[cnp.uint32_t, ndim=2] index = np.zeros((n_q, width),
+                                                            np.uint32)
+    cdef cnp.ndarray[cnp.float32_t, ndim=2] prob = np.zeros((n_q, width),
+                                                            np.float32)
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] w
+    cdef const uint32_t ** qc = <const uint32_t **> malloc(
+        sizeof(void *) * (nf + 1))
+    cdef size_t i
+    for i in range(nf):
+        w = qw[i]
+        qc[i] = <const uint32_t *> w.data
+    cdef dist_gibbs_t ** ptrs
+    cdef int rc
+    try:
+        ptrs = _engine_ptrs(engines)
+    except Exception:
+        free(qc)
+        raise
+    with nogil:
+        if single:
+            rc = dist_gibbs_search_resident(
+                ptrs[0], n_q, qc, row_begin, row_end, k, flags,
+                <uint32_t *> index.data, <float *> prob.data, stride)
+        else:
+            rc = dist_gibbs_search_resident_many(
+                <dist_gibbs_t * const *> ptrs, m, n_q, qc, row_begin, row_end,
+                k, flags, <uint32_t *> index.data, <float *> prob.data,
+                stride)
+    free(ptrs)
+    free(qc)
+    check(rc)
+    return (np.ascontiguousarray(index[:, :k]),
+            np.ascontiguousarray(prob[:, :k]))
+
+
+def coassign_resident_topk_many_dev(engines, size_t rows_ptr, size_t n_q,
+                                    size_t row_begin, size_t row_end,
+                                    size_t k, unsigned flags,
+                                    size_t index_ptr, size_t prob_ptr,
+                                    size_t ld, bint single=False):
+    """Per resident query row the k most co-assigned RESIDENT rows of
+    [row_begin, row_end) over M engines
+    (dist_gibbs_coassign_resident_topk_many_dev; single:
+    dist_gibbs_coassign_resident_topk_dev): device addresses of uint32 row
+    indices and of [n_q, ld] uint32 words and floats."""
+    cdef size_t m = len(engines)
+    if single and m != 1:
+        raise RuntimeError("coassign_resident_topk: one engine")
+    cdef dist_gibbs_t ** ptrs = _engine_ptrs(engines)
+    cdef int rc
+    with nogil:
+        if single:
+            rc = dist_gibbs_coassign_resident_topk_dev(
+                ptrs[0], <const uint32_t *> rows_ptr, n_q, row_begin, row_end,
+                k, flags, <uint32_t *> index_ptr, <float *> prob_ptr, ld)
+        else:
+            rc = dist_gibbs_coassign_resident_topk_many_dev(
+                <dist_gibbs_t * const *> ptrs, m,
+                <const uint32_t *> rows_ptr, n_q, row_begin, row_end, k,
+                flags, <uint32_t *> index_ptr, <float *> prob_ptr, ld)
+    free(ptrs)
+    check(rc)
+
+
+def coassign_resident_topk_many(engines, rows, size_t row_begin,
+                                size_t row_end, size_t k, unsigned flags=0,
+                                bint single=False, ld=None):
+    """coassign_resident_topk_many_dev from a host index array
+    (dist_gibbs_coassign_resident_topk_many; single:
+    dist_gibbs_coassign_resident_topk) -> (uint32 [n_q, k], float32 [n_q, k])"""
+    cdef size_t m = len(engines)
+    if single and m != 1:
+        raise RuntimeError("coassign_resident_topk: one engine")
+    cdef cnp.ndarray[cnp.uint32_t, ndim=1] ra = _row_indices(rows)
+    cdef size_t n_q = ra.shape[0]
+    cdef size_t stride = k if ld is None else ld
+    cdef size_t width = max(stride, k)
+    cdef cnp.ndarray[cnp.uint32_t, ndim=2] index = np.zeros((n_q, width),
+                                                            np.uint32)
+    cdef cnp.ndarray[cnp.float32_t, ndim=2] prob = np.zeros((n_q, width),
+                                                            np.float32)
+    cdef const uint32_t * pa = <const uint32_t *> ra.data
+    cdef dist_gibbs_t ** ptrs = _engine_ptrs(engines)
+    cdef int rc
+    with nogil:
+        if single:
+            rc = dist_gibbs_coassign_resident_topk(
+                ptrs[0], pa, n_q, row_begin, row_end, k, flags,
+                <uint32_t *> index.data, <float *> prob.data, stride)
+        else:
+            rc = dist_gibbs_coassign_resident_topk_many(
+                <dist_gibbs_t * const *> ptrs, m, pa, n_q, row_begin, row_end,
+                k, flags, <uint32_t *> index.data, <float *> prob.data,
+                stride)
+    free(ptrs)
     check(rc)
     return (np.ascontiguousarray(index[:, :k]),
             np.ascontiguousarray(prob[:, :k]))

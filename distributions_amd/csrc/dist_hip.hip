@@ -10,6 +10,7 @@
 // empty-group set, id maps) and a mirror of the integer group sizes.
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <atomic>
 #include <chrono>
@@ -6135,6 +6136,40 @@ struct Gibbs {
         dist_gibbs_t * const * engines, size_t m, const uint32_t * rows_a_dev,
         size_t na, const uint32_t * rows_b_dev, size_t nb, float * out_dev,
         size_t ld);
+    // per query the k most co-assigned RESIDENT rows (kernels_search.h):
+    // queries held-out rows (values) or resident rows (indices)
+    static void resident_topk(const std::string & who, bool held_out,
+                              dist_gibbs_t * const * engines, size_t m,
+                              size_t n_q,
+                              const uint32_t * const * values_dev,
+                              const uint32_t * rows_dev, size_t row_begin,
+                              size_t row_end, size_t k, unsigned flags,
+                              uint32_t * index_out_dev, float * prob_out_dev,
+                              size_t ld);
+    static void search_resident_many(dist_gibbs_t * const * engines, size_t m,
+                                     size_t n_q,
+                                     const uint32_t * const * values_dev,
+                                     size_t row_begin, size_t row_end,
+                                     size_t k, unsigned flags,
+                                     uint32_t * index_out_dev,
+                                     float * prob_out_dev, size_t ld) {
+        resident_topk("search_resident_many", true, engines, m, n_q,
+                      values_dev, nullptr, row_begin, row_end, k, flags,
+                      index_out_dev, prob_out_dev, ld);
+    }
+    static void coassign_resident_topk_many(
+            dist_gibbs_t * const * engines, size_t m,
+            const uint32_t * rows_dev, size_t n_q, size_t row_begin,
+            size_t row_end, size_t k, unsigned flags,
+            uint32_t * index_out_dev, float * prob_out_dev, size_t ld) {
+        resident_topk("coassign_resident_topk_many", false, engines, m, n_q,
+                      nullptr, rows_dev, row_begin, row_end, k, flags,
+                      index_out_dev, prob_out_dev, ld);
+    }
+    // the search's scratch, on the call's first engine
+    DeviceBuf<PartitionCol> search_cols;
+    DeviceBuf<const float *> search_planes;
+    DeviceBuf<uint32_t> search_qlab;
 };
 
 }  // namespace dist
@@ -6966,6 +7001,196 @@ void dist::Gibbs::coassign_topk_many(dist_gibbs_t * const * engines, size_t m,
     unsigned long long bad[2];
     memcpy(bad, pinned, sizeof(bad));
     coassign_require_domains(who, bad);
+}
+
+// Per query the k resident rows of [row_begin, row_end) it is most co-assigned
+// with over the engines (kernels_search.h).  Queries are held-out rows
+// (values_dev; phase A and its planes are coassign_many's) or resident rows
+// (rows_dev).  Slices of the targets go to workgroups, a launch's candidates
+// to k_coassign_topk_merge, which folds them into the call's running keys;
+// every report rides on the one download at the end.
+void dist::Gibbs::resident_topk(const std::string & who, bool held_out,
+                                dist_gibbs_t * const * engines, size_t m,
+                                size_t n_q,
+                                const uint32_t * const * values_dev,
+                                const uint32_t * rows_dev, size_t row_begin,
+                                size_t row_end, size_t k, unsigned flags,
+                                uint32_t * index_out_dev,
+                                float * prob_out_dev, size_t ld) {
+    DIST_REQUIRE(m == 0 || engines, "null argument");
+    DIST_REQUIRE((flags & ~DIST_COASSIGN_EXCLUDE_SELF) == 0,
+                 who + ": unknown flag");
+    const bool exclude = (flags & DIST_COASSIGN_EXCLUDE_SELF) != 0;
+    DIST_REQUIRE(!exclude || !held_out,
+                 who + ": DIST_COASSIGN_EXCLUDE_SELF needs the queries to be "
+                       "resident rows");
+    DIST_REQUIRE(k <= (size_t)kSearchList, who + ": k is at most 128");
+    DIST_REQUIRE(ld >= k, who + ": ld is less than k");
+    if (!m) return;
+    const std::vector<Gibbs *> e = resident_engines(engines, m, who);
+    if (held_out) (void)coassign_engines(engines, m, who);
+    Gibbs & first = *e[0];
+    const size_t n_rows = first.n_rows;
+    DIST_REQUIRE(row_begin <= row_end, who + ": row_begin is past row_end");
+    DIST_REQUIRE(row_end <= n_rows,
+                 who + ": row_end is past the engines' "
+                     + std::to_string(n_rows) + " rows");
+    // (a target's index is the low word's complement, and key 0 is no target)
+    DIST_REQUIRE(row_end <= 0xFFFFFFFFull,
+                 who + ": target rows are below 2^32 - 1");
+    if (!n_q || !k) return;
+    const int F = first.F();
+    DIST_REQUIRE(index_out_dev != nullptr && prob_out_dev != nullptr,
+                 "null argument");
+    if (held_out) {
+        DIST_REQUIRE(values_dev != nullptr || F == 0, "null argument");
+        for (int f = 0; f < F; ++f)
+            DIST_REQUIRE(values_dev[f] != nullptr, "null value column");
+    } else {
+        DIST_REQUIRE(rows_dev != nullptr, "null argument");
+    }
+    const size_t n_t = row_end - row_begin;
+    const size_t chunk = std::max<size_t>(1, (size_t)first.opt.predict_chunk);
+    const int kc = (int)k;
+    // the queries of a launch: at most a chunk, the planes (or the queries'
+    // labels) under 1 GiB, a grid dimension of blocks
+    std::vector<size_t> offs(m);
+    size_t k_rows = 0;
+    for (size_t i = 0; i < m; ++i) {
+        offs[i] = k_rows;
+        k_rows += (size_t)e[i]->K();
+    }
+    size_t step_q = std::min(n_q, chunk);
+    if (held_out) {
+        const size_t fit = kManyScratchWords / std::max<size_t>(1, k_rows);
+        DIST_REQUIRE(fit >= (size_t)kCoTile,
+                     who + ": the engines' groups leave no room for a tile "
+                           "of rows in 1 GiB of scratch");
+        if (coassign_pad_rows(step_q) > fit)
+            step_q = fit / kCoTile * kCoTile;
+    } else {
+        const size_t fit = kManyScratchWords / m / kSearchQ * kSearchQ;
+        step_q = std::min(step_q, fit);
+    }
+    step_q = std::min(step_q, (size_t)65535 * kSearchQ);
+    auto blocks = [](size_t rows) {
+        return (rows + kSearchQ - 1) / kSearchQ;
+    };
+    // the slices: enough workgroups for the device at the launch's blocks of
+    // queries, four tiles at least (a threshold needs rows to work on), a
+    // chunk at most; a launch's candidates under 1 GiB
+    constexpr size_t kWorkgroups = 256 * 4;
+    const size_t want = (kWorkgroups + blocks(step_q) - 1) / blocks(step_q);
+    size_t slice = std::max((n_t + want - 1) / want,
+                            (size_t)4 * kSearchTile);
+    slice = std::min(slice, chunk);
+    const size_t slices_all = (n_t + slice - 1) / slice;
+    const size_t room = (((size_t)1 << 30) - 1) / sizeof(unsigned long long);
+    const size_t per = std::max<size_t>(
+        1, std::min(std::max<size_t>(1, slices_all),
+                    room / (step_q * (size_t)kc)));
+    first.co_topk_cand.reserve(step_q * per * (size_t)kc, 0);
+    first.co_topk_run.reserve(n_q * k, 0);
+    unsigned long long * const run = first.co_topk_run.p;
+    HIP_CHECK(hipMemsetAsync(run, 0, n_q * k * sizeof(unsigned long long),
+                             stream()));
+    // the reports: a value outside its domain, a query index past the rows,
+    // a label without a slot
+    first.predict_bad.reserve(4, 0);
+    unsigned long long * const bad = first.predict_bad.p;
+    HIP_CHECK(hipMemsetAsync(bad, 0xFF, 3 * sizeof(unsigned long long),
+                             stream()));
+    std::vector<PartitionCol> cols(m);
+    memset(cols.data(), 0, m * sizeof(PartitionCol));
+    std::vector<PredictMember> args;
+    if (held_out) args = coassign_members(e);
+    for (size_t i = 0; i < m; ++i) {
+        e[i]->upload_maps();
+        cols[i].labels = e[i]->assign;
+        cols[i].g2p = e[i]->d_g2p_ptr;
+        cols[i].n_global = (uint32_t)e[i]->tracker.g2p.size();
+        cols[i].n_labels = (uint32_t)e[i]->K();
+    }
+    first.search_cols.upload(cols.data(), m);
+    ResidentTopk A;
+    memset(&A, 0, sizeof(A));
+    A.cols = first.search_cols.p;
+    A.m = (int)m;
+    A.kc = kc;
+    A.exclude = exclude ? 1 : 0;
+    A.slice = slice;
+    A.cand = first.co_topk_cand.p;
+    A.bad = bad + 2;
+    A.fm = (float)m;
+    if (held_out) {
+        A.ldq = coassign_pad_rows(step_q);
+        first.co_planes_q.reserve(std::max<size_t>(1, k_rows) * A.ldq, 0);
+        first.co_args_q.reserve(grow_capacity(m), 0);
+        std::vector<const float *> planes(m);
+        for (size_t i = 0; i < m; ++i)
+            planes[i] = first.co_planes_q.p + offs[i] * A.ldq;
+        first.search_planes.upload(planes.data(), m);
+        A.planes = first.search_planes.p;
+    } else {
+        A.ldl = blocks(step_q) * kSearchQ;
+        first.search_qlab.reserve(m * A.ldl, 0);
+        A.qlab = first.search_qlab.p;
+        LAUNCH(k_partition_rows_check, n_q, rows_dev, n_q, n_rows, bad + 1);
+    }
+    for (size_t cq = 0; cq < n_q; cq += step_q) {
+        const size_t rows_q = std::min(n_q, cq + step_q) - cq;
+        A.n_q = rows_q;
+        if (held_out) {
+            coassign_resp(e, args, first.co_args_q, values_dev, cq, rows_q,
+                          first.co_planes_q.p, offs, A.ldq,
+                          coassign_pad_rows(rows_q), 0, cq == 0, bad);
+        } else {
+            A.rows = rows_dev + cq;
+            LAUNCH(k_resident_query_labels, m * A.ldl, A.cols, (int)m, A.rows,
+                   rows_q, n_rows, first.search_qlab.p, A.ldl);
+        }
+        for (size_t s0 = 0; s0 < slices_all; s0 += per) {
+            const size_t ns = std::min(per, slices_all - s0);
+            A.t0 = row_begin + s0 * slice;
+            A.t1 = std::min(row_end, A.t0 + ns * slice);
+            A.slices = (unsigned)ns;
+            const dim3 grid((unsigned)ns, (unsigned)blocks(rows_q));
+            if (held_out)
+                hipLaunchKernelGGL(k_resident_topk<true>, grid, dim3(kBlock),
+                                   0, stream(), A);
+            else
+                hipLaunchKernelGGL(k_resident_topk<false>, grid, dim3(kBlock),
+                                   0, stream(), A);
+            HIP_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_coassign_topk_merge, dim3((unsigned)rows_q),
+                               dim3(kCoTopkMergeBlock), 0, stream(), A.cand,
+                               A.slices, kc, (int)k, run + cq * k);
+            HIP_CHECK(hipGetLastError());
+        }
+    }
+    hipLaunchKernelGGL(k_coassign_topk_decode, grid_for(n_q * k),
+                       dim3(kBlock), 0, stream(), run, n_q, (int)k,
+                       index_out_dev, prob_out_dev, ld);
+    HIP_CHECK(hipGetLastError());
+    // the call's one wait
+    char * pinned = chain_pinned(64);
+    HIP_CHECK(hipMemcpyAsync(pinned, bad, 3 * sizeof(unsigned long long),
+                             hipMemcpyDeviceToHost, stream()));
+    HIP_CHECK(hipStreamSynchronize(stream()));
+    unsigned long long got[3];
+    memcpy(got, pinned, sizeof(got));
+    DIST_REQUIRE(got[0] == ~0ull,
+                 who + ": value outside its feature's domain at row "
+                     + std::to_string(got[0] >> 8) + ", feature "
+                     + std::to_string(got[0] & 0xFF));
+    DIST_REQUIRE(got[1] == ~0ull,
+                 who + ": row index outside the engines' "
+                     + std::to_string(n_rows) + " rows at rows["
+                     + std::to_string(got[1]) + "]");
+    DIST_REQUIRE(got[2] == ~0ull,
+                 who + ": engine " + std::to_string(got[2] >> 32)
+                     + " holds a label without a slot at row "
+                     + std::to_string(got[2] & 0xFFFFFFFFull));
 }
 
 void dist::Gibbs::responsibilities(dist_gibbs_t * g, size_t n,
@@ -9604,6 +9829,144 @@ int dist_gibbs_coassign_resident(dist_gibbs_t * g, const uint32_t * rows_a,
                                  float * out, size_t ld) {
     return dist_gibbs_coassign_resident_many(&g, 1, rows_a, na, rows_b, nb,
                                              out, ld);
+}
+int dist_gibbs_search_resident_many_dev(
+        dist_gibbs_t * const * engines, size_t m, size_t n_q,
+        const uint32_t * const * values_dev, size_t row_begin, size_t row_end,
+        size_t k, unsigned flags, uint32_t * index_out_dev,
+        float * prob_out_dev, size_t ld) {
+    return guarded([&] {
+        ensure_device_ready();
+        Gibbs::search_resident_many(engines, m, n_q, values_dev, row_begin,
+                                    row_end, k, flags, index_out_dev,
+                                    prob_out_dev, ld);
+    });
+}
+// the host forms' results: [n_q, k] on the device, then into the caller's
+// [n_q, ld]
+static void search_resident_host(
+        size_t n_q, size_t k, bool work, uint32_t * index_out,
+        float * prob_out, size_t ld,
+        const std::function<void(uint32_t *, float *)> & call) {
+    DeviceBuf<uint32_t> index;
+    DeviceBuf<float> prob;
+    if (work && k <= (size_t)dist::kSearchList) {
+        DIST_REQUIRE(index_out != nullptr && prob_out != nullptr,
+                     "null argument");
+        index.reserve(n_q * k, 0);
+        prob.reserve(n_q * k, 0);
+    }
+    call(index.p, prob.p);
+    if (!work) return;
+    HIP_CHECK(hipMemcpy2DAsync(index_out, ld * sizeof(uint32_t), index.p,
+                               k * sizeof(uint32_t), k * sizeof(uint32_t),
+                               n_q, hipMemcpyDeviceToHost, stream()));
+    HIP_CHECK(hipMemcpy2DAsync(prob_out, ld * sizeof(float), prob.p,
+                               k * sizeof(float), k * sizeof(float), n_q,
+                               hipMemcpyDeviceToHost, stream()));
+    dist::sync();
+}
+int dist_gibbs_search_resident_many(
+        dist_gibbs_t * const * engines, size_t m, size_t n_q,
+        const uint32_t * const * values, size_t row_begin, size_t row_end,
+        size_t k, unsigned flags, uint32_t * index_out, float * prob_out,
+        size_t ld) {
+    return guarded([&] {
+        ensure_device_ready();
+        DIST_REQUIRE(m == 0 || engines, "null argument");
+        const std::string who = "search_resident_many";
+        // (the limits on k and ld are the device form's: its ld here is k)
+        DIST_REQUIRE(ld >= k, who + ": ld is less than k");
+        std::vector<DeviceBuf<uint32_t>> cols;
+        std::vector<const uint32_t *> ptrs(1);
+        const bool work = m && engines[0] && n_q && k;
+        if (work) {
+            const int F = engines[0]->impl.read()->F();
+            DIST_REQUIRE(values != nullptr || F == 0, "null argument");
+            cols.resize((size_t)F);
+            ptrs.resize((size_t)F + 1);
+            for (int f = 0; f < F; ++f) {
+                DIST_REQUIRE(values[f] != nullptr, "null value column");
+                cols[f].upload(values[f], n_q);
+                ptrs[f] = cols[f].p;
+            }
+        }
+        search_resident_host(
+            n_q, k, work, index_out, prob_out, ld,
+            [&](uint32_t * index, float * prob) {
+                Gibbs::search_resident_many(engines, m, n_q, ptrs.data(),
+                                            row_begin, row_end, k, flags,
+                                            index, prob, k);
+            });
+    });
+}
+int dist_gibbs_search_resident_dev(
+        dist_gibbs_t * g, size_t n_q, const uint32_t * const * values_dev,
+        size_t row_begin, size_t row_end, size_t k, unsigned flags,
+        uint32_t * index_out_dev, float * prob_out_dev, size_t ld) {
+    return dist_gibbs_search_resident_many_dev(
+        &g, 1, n_q, values_dev, row_begin, row_end, k, flags, index_out_dev,
+        prob_out_dev, ld);
+}
+int dist_gibbs_search_resident(
+        dist_gibbs_t * g, size_t n_q, const uint32_t * const * values,
+        size_t row_begin, size_t row_end, size_t k, unsigned flags,
+        uint32_t * index_out, float * prob_out, size_t ld) {
+    return dist_gibbs_search_resident_many(&g, 1, n_q, values, row_begin,
+                                           row_end, k, flags, index_out,
+                                           prob_out, ld);
+}
+int dist_gibbs_coassign_resident_topk_many_dev(
+        dist_gibbs_t * const * engines, size_t m, const uint32_t * rows_dev,
+        size_t n_q, size_t row_begin, size_t row_end, size_t k,
+        unsigned flags, uint32_t * index_out_dev, float * prob_out_dev,
+        size_t ld) {
+    return guarded([&] {
+        ensure_device_ready();
+        Gibbs::coassign_resident_topk_many(engines, m, rows_dev, n_q,
+                                           row_begin, row_end, k, flags,
+                                           index_out_dev, prob_out_dev, ld);
+    });
+}
+int dist_gibbs_coassign_resident_topk_many(
+        dist_gibbs_t * const * engines, size_t m, const uint32_t * rows,
+        size_t n_q, size_t row_begin, size_t row_end, size_t k,
+        unsigned flags, uint32_t * index_out, float * prob_out, size_t ld) {
+    return guarded([&] {
+        ensure_device_ready();
+        DIST_REQUIRE(m == 0 || engines, "null argument");
+        const std::string who = "coassign_resident_topk_many";
+        DIST_REQUIRE(ld >= k, who + ": ld is less than k");
+        const bool work = m && engines[0] && n_q && k;
+        DeviceBuf<uint32_t> staged;
+        if (work) {
+            DIST_REQUIRE(rows != nullptr, "null argument");
+            staged.upload(rows, n_q);
+        }
+        search_resident_host(
+            n_q, k, work, index_out, prob_out, ld,
+            [&](uint32_t * index, float * prob) {
+                Gibbs::coassign_resident_topk_many(
+                    engines, m, staged.p, n_q, row_begin, row_end, k, flags,
+                    index, prob, k);
+            });
+    });
+}
+int dist_gibbs_coassign_resident_topk_dev(
+        dist_gibbs_t * g, const uint32_t * rows_dev, size_t n_q,
+        size_t row_begin, size_t row_end, size_t k, unsigned flags,
+        uint32_t * index_out_dev, float * prob_out_dev, size_t ld) {
+    return dist_gibbs_coassign_resident_topk_many_dev(
+        &g, 1, rows_dev, n_q, row_begin, row_end, k, flags, index_out_dev,
+        prob_out_dev, ld);
+}
+int dist_gibbs_coassign_resident_topk(
+        dist_gibbs_t * g, const uint32_t * rows, size_t n_q, size_t row_begin,
+        size_t row_end, size_t k, unsigned flags, uint32_t * index_out,
+        float * prob_out, size_t ld) {
+    return dist_gibbs_coassign_resident_topk_many(
+        &g, 1, rows, n_q, row_begin, row_end, k, flags, index_out, prob_out,
+        ld);
 }
 size_t dist_gibbs_group_count(const dist_gibbs_t * g) {
     size_t n = (size_t)-1;

@@ -37,3 +37,4 @@ constexpr size_t kLdsWorkgroupLimit = 144 * 1024;
 #include "kernels_apply.h"
 #include "kernels_hyper.h"
 #include "kernels_partitions.h"
+#include "kernels_search.h"

@@ -235,6 +235,30 @@ class Gibbs(object):
         return _coassign_topk_torch([self], values, other, k, exclude_self,
                                     True)
 
+    def search_resident(self, values, k=10, row_begin=0, row_end=None):
+        """search_resident_many on this engine alone
+        (dist_gibbs_search_resident) -> (index int32 [n, k], prob [n, k])"""
+        return _search_resident([self], values, k, row_begin, row_end, True)
+
+    def search_resident_torch(self, values, k=10, row_begin=0, row_end=None):
+        """search_resident for device tensors -> two [n, k] tensors"""
+        return _search_resident_torch([self], values, k, row_begin, row_end,
+                                      True)
+
+    def coassign_resident_topk(self, rows, k=10, exclude_self=True,
+                               row_begin=0, row_end=None):
+        """coassign_resident_topk_many on this engine alone
+        (dist_gibbs_coassign_resident_topk): the k lowest-indexed rows of
+        rows[a]'s own group, then of the others"""
+        return _coassign_resident_topk([self], rows, k, exclude_self,
+                                       row_begin, row_end, True)
+
+    def coassign_resident_topk_torch(self, rows, k=10, exclude_self=True,
+                                     row_begin=0, row_end=None):
+        """coassign_resident_topk for a device index tensor"""
+        return _coassign_resident_topk_torch([self], rows, k, exclude_self,
+                                             row_begin, row_end, True)
+
     def predict_feature(self, values, target, candidates=None, observed=None,
                         mode="map", seed=0, draw_base=0, staged=True):
         """Given some cells of rows that are NOT in the table, the cell that
@@ -889,6 +913,118 @@ def coassign_topk_many_torch(engines, values, other=None, k=10,
     device; nothing is staged through the host."""
     return _coassign_topk_torch(engines, values, other, k, exclude_self,
                                 False)
+
+
+def _resident_range(engines, row_begin, row_end):
+    """row_end None: the first engine's row count"""
+    if row_end is None:
+        first = engines[0] if engines else None
+        row_end = 0 if first is None else first.core.row_count()
+    return int(row_begin), int(row_end)
+
+
+def _search_resident(engines, values, k, row_begin, row_end, single):
+    row_begin, row_end = _resident_range(engines, row_begin, row_end)
+    index, prob = _core.search_resident_many(
+        _cores(engines), list(values), row_begin, row_end, k, 0, single)
+    return index.view(np.int32), prob
+
+
+def search_resident_many(engines, values, k=10, row_begin=0, row_end=None):
+    """Which rows of the table are most like this record: for every row q of
+    `values` (rows that are NOT in the table, one host array per feature) the
+    k RESIDENT rows b of [row_begin, row_end) (None: every row) it most likely
+    shares a slot with, over M engines that hold the same rows in the same
+    order.  -> (index int32 [n, k], prob float32 [n, k]).
+    prob = (1/M) sum_e r_e,q[slot_e(b)] with r = `responsibilities` and
+    slot_e(b) the group row b has in engine e: the probability that
+    `predict(mode="sample")` puts q into the slot b occupies, the engine drawn
+    uniformly.  It is not normalised over b, and rows that share a group in
+    every engine have bit-equal cells: with one engine the k targets are the k
+    lowest-indexed rows of the best group; it takes several chains to tell
+    rows apart.  Targets by prob descending, among bit-equal cells by index
+    ascending; index is the row's index in the table; where the range has
+    fewer than k rows the rest is index -1 and probability +0.  k is at most
+    128.  A row whose logp is not finite on some engine has an unspecified
+    result row.  Nothing in the engines changes."""
+    return _search_resident(list(engines), values, k, row_begin, row_end,
+                            False)
+
+
+def _search_resident_torch(engines, values, k, row_begin, row_end, single):
+    import torch
+    row_begin, row_end = _resident_range(engines, row_begin, row_end)
+    values = _device_columns(values)
+    n_q = int(values[0].numel())
+    dev = values[0].device
+    k = int(k)
+    index = torch.empty((n_q, k), dtype=torch.int32, device=dev)
+    prob = torch.empty((n_q, k), dtype=torch.float32, device=dev)
+    # (the library works on its own stream: what filled the tensors on
+    # torch's must be done)
+    torch.cuda.current_stream(dev).synchronize()
+    _core.search_resident_many_dev(
+        _cores(engines), [int(v.data_ptr()) for v in values], n_q, row_begin,
+        row_end, k, 0, int(index.data_ptr()), int(prob.data_ptr()), k, single)
+    return index, prob
+
+
+def search_resident_many_torch(engines, values, k=10, row_begin=0,
+                               row_end=None):
+    """search_resident_many for device tensors (one 4-byte-per-row CUDA
+    tensor per feature) -> two [n, k] tensors on the same device; nothing is
+    staged through the host."""
+    return _search_resident_torch(list(engines), values, k, row_begin,
+                                  row_end, False)
+
+
+def _coassign_resident_topk(engines, rows, k, exclude_self, row_begin,
+                            row_end, single):
+    row_begin, row_end = _resident_range(engines, row_begin, row_end)
+    index, prob = _core.coassign_resident_topk_many(
+        _cores(engines), rows, row_begin, row_end, k,
+        _core.COASSIGN_EXCLUDE_SELF if exclude_self else 0, single)
+    return index.view(np.int32), prob
+
+
+def coassign_resident_topk_many(engines, rows, k=10, exclude_self=True,
+                                row_begin=0, row_end=None):
+    """Which rows of the table are most like this row of the table: for every
+    index rows[a] the k RESIDENT rows b of [row_begin, row_end) (None: every
+    row) that share its group in the most of the M engines -- the k largest
+    cells of `coassign_resident_many(engines, rows, arange(N))`'s row a, bit
+    for bit, without the [n, N] matrix.  -> (index int32 [n, k], prob float32
+    [n, k]), ordered and filled as `search_resident_many`'s.  exclude_self
+    leaves b == rows[a] out (the row, not the position: duplicates in `rows`
+    are legal).  Nothing in the engines changes."""
+    return _coassign_resident_topk(list(engines), rows, k, exclude_self,
+                                   row_begin, row_end, False)
+
+
+def _coassign_resident_topk_torch(engines, rows, k, exclude_self, row_begin,
+                                  row_end, single):
+    import torch
+    row_begin, row_end = _resident_range(engines, row_begin, row_end)
+    ra = _device_rows(rows)
+    dev = ra.device
+    n_q = int(ra.numel())
+    k = int(k)
+    index = torch.empty((n_q, k), dtype=torch.int32, device=dev)
+    prob = torch.empty((n_q, k), dtype=torch.float32, device=dev)
+    torch.cuda.current_stream(dev).synchronize()
+    _core.coassign_resident_topk_many_dev(
+        _cores(engines), int(ra.data_ptr()), n_q, row_begin, row_end, k,
+        _core.COASSIGN_EXCLUDE_SELF if exclude_self else 0,
+        int(index.data_ptr()), int(prob.data_ptr()), k, single)
+    return index, prob
+
+
+def coassign_resident_topk_many_torch(engines, rows, k=10, exclude_self=True,
+                                      row_begin=0, row_end=None):
+    """coassign_resident_topk_many for a device index tensor -> two [n, k]
+    tensors on the same device; nothing is staged through the host."""
+    return _coassign_resident_topk_torch(list(engines), rows, k, exclude_self,
+                                         row_begin, row_end, False)
 
 
 def predict_feature_many(engines, values, target, candidates=None,

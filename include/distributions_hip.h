@@ -1236,6 +1236,88 @@ int dist_gibbs_coassign_resident(dist_gibbs_t * g, const uint32_t * rows_a,
                                  size_t na, const uint32_t * rows_b, size_t nb,
                                  float * out, size_t ld);
 
+/* Which rows of the table are most like this one: per query the k RESIDENT
+ * rows b of [row_begin, row_end) it is most co-assigned with over m engines
+ * that hold the same rows in the same order, without the [n_q, N] matrix.
+ * Two kinds of query, one target set, one order and one fill.
+ * dist_gibbs_search_resident_many: queries are held-out rows, values[f][q] as
+ * dist_gibbs_coassign_many takes them.  With r_e,q[k] bit for bit
+ * dist_gibbs_responsibilities' value and slot_e(b) the packed index of the
+ * group resident row b has in engine e (dist_gibbs_global_to_packed of its
+ * assignment),
+ *     acc = 0.0f; engines ascending: acc = acc + r_e,q[slot_e(b)]
+ *     cell(q, b) = acc / (float)m            (IEEE division)
+ * one chain of binary32 adds.  It is the probability that dist_gibbs_predict's
+ * draw puts q into the slot b occupies, the engine drawn uniformly.  It is NOT
+ * normalised over b (it sums to the mean group size), and rows that share a
+ * group in every engine have bit-equal cells: with one engine a query's k
+ * targets are the k lowest-indexed rows of its best group, and it takes
+ * several chains to tell rows apart.  A query whose logp is not finite on some
+ * engine has an unspecified result row; targets are never scored.
+ * dist_gibbs_coassign_resident_topk_many: queries are resident rows rows[a].
+ *     cell(a, b) = (float)c / (float)m
+ * c the engines in which rows[a] and b carry the same group id: bit for bit
+ * dist_gibbs_coassign_resident_many's cell.  With DIST_COASSIGN_EXCLUDE_SELF
+ * b == rows[a] is left out -- the row, not the position: duplicate queries are
+ * legal.  The flag is legal only here.
+ * Order and fill are dist_gibbs_coassign_topk_many's: targets by cell
+ * descending and among bit-equal cells by b ascending, the descending order of
+ * key = (uint64(bits(cell)) << 32) | (0xFFFFFFFF - b); where fewer than k
+ * targets exist the rest is index 0xFFFFFFFF, prob +0.0f.  index_out[q * ld +
+ * j] is the row's index in the engine, not its offset in the range.
+ * 1 <= k <= 128, ld >= k, row_end <= 2^32 - 1.  The result does not depend on
+ * slices, chunks or launch geometry.  m == 0, n_q == 0 or k == 0 does nothing;
+ * an empty range writes the fill.
+ * Refused: what dist_gibbs_coassign_resident_many refuses of the engines
+ * (unequal row counts, unassigned rows, the same engine twice, an open
+ * batch); for held-out queries also what dist_gibbs_coassign_many refuses
+ * (feature lists or clustering models that differ, stale cells);
+ * row_begin > row_end or row_end > the row count; a query index >= the row
+ * count, naming rows[i]; a value outside its feature's domain, naming row and
+ * feature; a resident label without a slot (an engine bug), naming engine and
+ * row.  The last three are found on the device and ride on the call's one
+ * download: one host wait per call.  Scratch: the planes of a chunk of
+ * queries and the candidates, 8 k bytes per (query, slice of the targets),
+ * each under 1 GiB; "debug.predict_chunk" of the first engine bounds a slice's
+ * rows and a chunk's queries.  The engines are read as dist_gibbs_assignments
+ * reads them; nothing in them changes.
+ * _dev: value columns, row indices and outputs are device pointers.
+ * dist_gibbs_search_resident and dist_gibbs_coassign_resident_topk: m == 1. */
+int dist_gibbs_search_resident_many_dev(
+    dist_gibbs_t * const * engines, size_t m, size_t n_q,
+    const uint32_t * const * values_dev, size_t row_begin, size_t row_end,
+    size_t k, unsigned flags, uint32_t * index_out_dev, float * prob_out_dev,
+    size_t ld);
+int dist_gibbs_search_resident_many(
+    dist_gibbs_t * const * engines, size_t m, size_t n_q,
+    const uint32_t * const * values, size_t row_begin, size_t row_end,
+    size_t k, unsigned flags, uint32_t * index_out, float * prob_out,
+    size_t ld);
+int dist_gibbs_search_resident_dev(
+    dist_gibbs_t * g, size_t n_q, const uint32_t * const * values_dev,
+    size_t row_begin, size_t row_end, size_t k, unsigned flags,
+    uint32_t * index_out_dev, float * prob_out_dev, size_t ld);
+int dist_gibbs_search_resident(
+    dist_gibbs_t * g, size_t n_q, const uint32_t * const * values,
+    size_t row_begin, size_t row_end, size_t k, unsigned flags,
+    uint32_t * index_out, float * prob_out, size_t ld);
+int dist_gibbs_coassign_resident_topk_many_dev(
+    dist_gibbs_t * const * engines, size_t m, const uint32_t * rows_dev,
+    size_t n_q, size_t row_begin, size_t row_end, size_t k, unsigned flags,
+    uint32_t * index_out_dev, float * prob_out_dev, size_t ld);
+int dist_gibbs_coassign_resident_topk_many(
+    dist_gibbs_t * const * engines, size_t m, const uint32_t * rows,
+    size_t n_q, size_t row_begin, size_t row_end, size_t k, unsigned flags,
+    uint32_t * index_out, float * prob_out, size_t ld);
+int dist_gibbs_coassign_resident_topk_dev(
+    dist_gibbs_t * g, const uint32_t * rows_dev, size_t n_q, size_t row_begin,
+    size_t row_end, size_t k, unsigned flags, uint32_t * index_out_dev,
+    float * prob_out_dev, size_t ld);
+int dist_gibbs_coassign_resident_topk(
+    dist_gibbs_t * g, const uint32_t * rows, size_t n_q, size_t row_begin,
+    size_t row_end, size_t k, unsigned flags, uint32_t * index_out,
+    float * prob_out, size_t ld);
+
 size_t dist_gibbs_group_count(const dist_gibbs_t * g);     /* counts().size() */
 size_t dist_gibbs_row_count(const dist_gibbs_t * g);
 int dist_gibbs_counts(const dist_gibbs_t * g, int * out);  /* driver counts() */
