@@ -64,7 +64,10 @@ SINGLES = ["dd", "gp_nich", "dd_bb_gp", "dpd", "bnb", "le_dd", "le_gp_nich",
            "only_empty_k3", "dd_swept", "gp_nich_swept", "nich2", "dpd_swept",
            "dd256_k1025"]
 ENSEMBLES = {"ens3_dd_bb_gp": "dd_bb_gp", "ens3_gp_nich": "gp_nich"}
-NAMES = SINGLES + sorted(ENSEMBLES)
+# eight_expect's subjects over the eight-feature list (100 held-out rows):
+# one engine after two sweeps, and the ensemble of three
+WIDE = ["eight_swept", "eight3"]
+NAMES = SINGLES + sorted(ENSEMBLES) + WIDE
 
 
 def flush(x):
@@ -180,17 +183,22 @@ class Subject(object):
 
     def __init__(self, name):
         self.name = name
-        if name in ENSEMBLES:
+        self.many = name in ENSEMBLES or name == "eight3"
+        if name in WIDE:
+            import eight_expect as xe
+            self.src = xe.eight3() if self.many else xe.case(name)
+        elif self.many:
             self.src = ee.Ensemble(ENSEMBLES[name], ee.SPECS3)
-            self.members = self.src.members
         else:
             self.src = pe.case(name)
-            self.members = [self.src]
+        self.members = self.src.members if self.many else [self.src]
         self.M = len(self.members)
         self.qvals = self.src.qvals
         big = max(m.K for m in self.members) > 256
         self.rq = np.arange(40 if big else 70)
         self.rt = np.arange(100, 125 if big else 145)
+        if name in WIDE:
+            self.rq, self.rt = np.arange(56), np.arange(56, 100)
         self._r = None
         self._expect = {}
         self._law = {}
@@ -203,12 +211,12 @@ class Subject(object):
 
     def scores(self):
         """per engine [nq_all, K_e] float32"""
-        if self.name in ENSEMBLES:
+        if self.many:
             return [p["scores"] for p in self.src.expect()["per_member"]]
         return [self.src.expect()["scores"]]
 
     def logp(self):
-        if self.name in ENSEMBLES:
+        if self.many:
             return [p["logp"] for p in self.src.expect()["per_member"]]
         return [self.src.expect()["logp"]]
 

@@ -134,3 +134,22 @@ def test_pairs_of_independent_draws_agree_with_the_law(name):
         p = float(C[a, b])
         sigma = np.sqrt(max(p * (1 - p), 1e-12) / N)
         assert abs(hits / N - p) <= 4.5 * sigma + 1e-9, (a, b, hits / N, p)
+
+
+@pytest.mark.parametrize("variant", ["drop", "wrap"])
+@pytest.mark.parametrize("name", ce.WIDE)
+def test_wide_planted_variants_leave_the_band(name, variant):
+    """eight features: a law without feature 7, or with feature f's words
+    taken from feature f & 3, is outside the band on some cell"""
+    import eight_expect as xe
+    sub = ce.subject(name)
+    planted = [xe.planted_state(m.st, sub.qvals, variant)
+               for m in sub.members]
+    cols = planted[0][1]
+    C, _ = ce.law_f64([p[0] for p in planted],
+                      [np.ascontiguousarray(c[sub.rq]) for c in cols],
+                      [np.ascontiguousarray(c[sub.rt]) for c in cols])
+    exc = excursion(C, sub, False)
+    print("%s, %s: %.0f %% of the cells leave the band" % (
+        name, variant, 100.0 * (exc > 1.0).mean()))
+    assert exc.max() > 1.0

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 from scipy import stats
 
+import eight_expect as xe
 import ensemble_expect as ee
 import oracle_lib as ol
 import predict_expect as pe
@@ -152,3 +153,34 @@ def test_one_member_is_predict_itself(name):
         assert np.all(one["member_map"] == 0)
         assert np.array_equal(one["group_draw"], p["draw"])
         assert np.array_equal(one["group_map"], p["map"])
+
+
+# ---------------------------------------------------------------------------
+# the eight-feature ensemble of tests/eight_expect.py
+
+
+def test_eight3_expectation_is_in_the_float64_band():
+    """every held-out row, none left out"""
+    ens = xe.eight3()
+    e = ens.expect()
+    assert e["w"].shape == (3, ens.nq)
+    assert np.all(np.isfinite(e["logp"]))
+    assert len({m.K for m in ens.members}) == 3
+    x = ee.excursion(e["logp"], ens)
+    print("eight3: K = %s, %d held-out rows; worst excursion / band %.3f; "
+          "member draws %s" % ([m.K for m in ens.members], ens.nq, x.max(),
+                               np.bincount(e["member_draw"], minlength=3)))
+    assert x.max() <= 1.0
+
+
+@pytest.mark.parametrize("variant", ["drop", "wrap"])
+def test_eight3_planted_variants_leave_the_band(variant):
+    ens = xe.eight3()
+    Lv, band, _ = ens.f64()
+    planted = [xe.planted_state(m.st, ens.qvals, variant)
+               for m in ens.members]
+    wrong, _, _ = ee.law_f64([p[0] for p in planted], planted[0][1], False)
+    out = np.abs(wrong - Lv) > band
+    print("eight3, %s: %.0f %% of the held-out rows leave the band" % (
+        variant, 100.0 * out.mean()))
+    assert out.any()

@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 from scipy import stats
 
+import eight_expect as xe
 import ensemble_expect as ee
 import feature_expect as fe
 import feature_many_expect as fm
@@ -256,3 +257,61 @@ def test_one_member_is_predict_feature_itself(name):
         assert np.array_equal(one["choice_map"], first)
         assert np.all(one["member_draw"] == 0)
         assert np.all(one["member_map"] == 0)
+
+
+# ---------------------------------------------------------------------------
+# the eight-feature ensemble of tests/eight_expect.py
+
+
+def eight3_case(target, n):
+    ens = xe.eight3()
+    sh = ens.members[0].osh[target]
+    cand = fe.candidates_for(sh)
+    key = ("eight3", target, n)
+    if key not in _FENS:
+        f = fm.FeatureEnsemble(ens, target, cand,
+                               xe.masks_for(n, 8, MASK_SEED + target))
+        f.nq = n
+        _FENS[key] = f
+    return _FENS[key]
+
+
+@pytest.mark.parametrize("target", xe.TARGETS8)
+def test_eight3_joint_and_base_are_in_the_float64_band(target):
+    """every candidate on every one of the first n held-out rows (n = 40;
+    12 for DD70's 70 candidates, 20 for DPD's 21) under random and fixed
+    masks; the GPU test holds all 100 rows of targets 0, 3 and 7; the planted
+    variants (a feature >= 4 never observed, feature f's words from feature
+    f & 3, the mask through & 0xF) leave the band"""
+    # (DD70's 70 candidates on the rows of the fixed masks alone, DPD's 21
+    # on half the rows)
+    n = {4: 12, 6: 20}.get(target, 40)
+    fens = eight3_case(target, n)
+    ens = fens.ens
+    q = [v[:n] for v in ens.qvals]
+    L = ol.oracle()
+    e = fm.expect_many([m.orc for m in ens.members], q, fens.observed,
+                       target, fens.cand, L.orc_rng_seed(fm.DRAW_SEED),
+                       L.orc_rng_seed(fm.MEMBER_SEED), fm.DRAW_BASE, False)
+    states = [m.st for m in ens.members]
+    law = fm.law_f64(states, q, fens.observed, target, fens.values, False)
+    assert np.all(np.isfinite(e["joint"])) and np.all(np.isfinite(e["base"]))
+    xj = np.abs(e["joint"] - law["joint"]) / law["joint_band"]
+    xb = np.abs(e["base"] - law["base"]) / law["base_band"]
+    print("eight3 target %d: %d rows x %d candidates; worst excursion / "
+          "band: joint %.3f, base %.3f" % (target, n, fens.C, xj.max(),
+                                           xb.max()))
+    assert xj.max() <= 1.0 and xb.max() <= 1.0
+    for variant in xe.VARIANTS:
+        drop = 6 if target == 7 else 7
+        qq = xe.planted_state(states[0], q, "wrap" if variant == "wrap"
+                              else "mask4")[1]
+        wrong = fm.law_f64(states, qq,
+                           xe.planted_mask(fens.observed, variant, drop),
+                           target, fens.values, False)
+        out = ((np.abs(wrong["joint"] - law["joint"])
+                > law["joint_band"]).any(1)
+               | (np.abs(wrong["base"] - law["base"]) > law["base_band"]))
+        print("  %s: %.0f %% of the rows leave the band" % (
+            variant, 100.0 * out.mean()))
+        assert out.any(), variant

@@ -20,6 +20,7 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+import eight_expect as xe  # noqa: E402
 import ensemble_expect as ee  # noqa: E402
 import oracle_lib as ol  # noqa: E402
 import predict_expect as pe  # noqa: E402
@@ -54,6 +55,8 @@ ENSEMBLES = {
                      ee.SPECS3[2]]),
     "dd256_k1025": lambda: ee.Ensemble("dd", BIG3, nq=256, dim=256),
     "small130": lambda: ee.Ensemble("dd", SMALL130, nq=257),
+    # eight features, K = 8, 34 and 43 (tests/eight_expect.py)
+    "eight3": lambda: xe.eight3(),
 }
 _ENS = {}
 _GPUS = {}
@@ -127,6 +130,8 @@ def test_predict_many_is_the_oracles_bit_for_bit(name):
     assert np.array_equal(group, e["group_draw"])
     assert np.array_equal(group_m, e["group_map"])
     if name != "dpd_other_mixed":   # (the band takes no fast_log(0))
+        print("%s: worst excursion / band %.3f" % (
+            name, ee.excursion(logp, ens).max()))
         assert ee.excursion(logp, ens).max() <= 1.0
     # the draw-all form: the same bits
     for mode, m_key, g_key in (("sample", "member_draw", "group_draw"),
@@ -138,7 +143,8 @@ def test_predict_many_is_the_oracles_bit_for_bit(name):
         assert np.array_equal(group_a, e[g_key])
 
 
-@pytest.mark.parametrize("name", ["gp_nich", "le_dd_m5", "dpd_other_mixed"])
+@pytest.mark.parametrize("name", ["gp_nich", "le_dd_m5", "dpd_other_mixed",
+                                  "eight3"])
 def test_identities_with_predict(name):
     ens = ensemble(name)
     gpus = engines_of(name)

@@ -35,7 +35,7 @@ import sample_expect as sx  # noqa: E402
 import sample_many_expect as sm  # noqa: E402
 from test_gpu_predict import same, snapshot  # noqa: E402
 from test_gpu_predict_feature_many import (  # noqa: E402
-    ENSEMBLES, K4_K1025, same_bits)
+    ENSEMBLES, K4_K1025, masks_of, same_bits)
 # (without the entry point there is nothing to test: the module does not load)
 from distributions_amd.engine import (  # noqa: E402,F401
     sample_rows_many, sample_rows_many_torch)
@@ -147,6 +147,7 @@ CASES = {
     "le_m2": ("le_m2", 0, None),
     "le_m5": ("le_m5", 1, None),
     "only_empty_member": ("only_empty_member", 1, None),
+    "eight3": ("eight3", 7, None),
 }
 
 
@@ -160,7 +161,7 @@ def test_sample_rows_many_is_the_expectation_bit_for_bit(name):
     n = min(ens.nq, 96)
     q = [v[:n] for v in ens.qvals]
     full = (1 << F) - 1
-    masks = fe.random_masks(n, F, MASK_SEED)
+    masks = masks_of(n, F, MASK_SEED)
     cells = wrong = 0
     # per-row masks; a zero mask and no mask (both instances); everything
     # observed

@@ -17,7 +17,9 @@ import numpy as np
 import pytest
 from scipy import stats
 
+import eight_expect as xe
 import feature_expect as fe
+import feature_many_expect as fm
 import oracle_lib as ol
 import predict_expect as pe
 
@@ -121,3 +123,91 @@ def test_nothing_observed_gives_the_drivers_log_sum_exp(name, target):
         pe.expect(c.orc, q, seed_state(), 0)["prior_total"]).view(np.uint32)
     # and every row's joint is then the same
     assert np.all(e["joint"].view(np.uint32) == e["joint"][0].view(np.uint32))
+
+
+# ---------------------------------------------------------------------------
+# five to eight features (tests/eight_expect.py), under per-row masks
+
+
+def wide_law(c, q, masks, target, values):
+    """feature_many_expect.law_f64 over the one member: the float64 joint and
+    base of every row over the features its mask observes, and their bands
+    (the fold over one member adds orc_fast_log(1) = 0 and one eps)"""
+    return fm.law_f64([c.st], q, masks, target, values, False)
+
+
+WIDE = [(name, t) for name in ("eight", "eight_swept")
+        for t in xe.TARGETS8] + [("real_first", 0), ("real_first", 1),
+                                 ("real_first", 4)]
+
+
+@pytest.mark.parametrize("name,target", WIDE)
+def test_wide_joint_and_base_are_in_the_float64_band(name, target):
+    """every candidate on every one of the first n held-out rows (n = NROWS,
+    15 for DD70's 70 candidates), under random masks and the fixed ones (only
+    features >= 4, only features < 4, alternating)"""
+    c = xe.case(name)
+    F = len(c.osh)
+    sh = c.osh[target]
+    cand = fe.candidates_for(sh)
+    # (DD70's 70 candidates on the rows of the fixed masks and three more)
+    n = 15 if sh.kind == ol.DD and sh.dim > 30 else NROWS
+    q = head(c, n)
+    masks = xe.masks_for(n, F, 100 + target)
+    e = fe.expect(c.orc, q, masks, target, cand, seed_state(), pe.DRAW_BASE)
+    assert np.all(np.isfinite(e["joint"])) and np.all(np.isfinite(e["base"]))
+    values = fm.candidate_values(sh, cand)
+    law = wide_law(c, q, masks, target, values)
+    xj = np.abs(e["joint"] - law["joint"]) / law["joint_band"]
+    xb = np.abs(e["base"] - law["base"]) / law["base_band"]
+    print("%s target %d: %d candidates, worst excursion / band: joint %.3f, "
+          "base %.3f" % (name, target, len(values), xj.max(), xb.max()))
+    assert xj.max() <= 1.0 and xb.max() <= 1.0
+    # the planted variants leave the band the oracle is inside
+    if not any(f >= 4 and f != target for f in range(F)):
+        return              # (no feature >= 4 besides the target)
+    for variant in xe.VARIANTS:
+        drop = F - 2 if target == F - 1 else F - 1
+        if variant == "drop" and drop < 4:
+            continue        # (no feature >= 4 besides the target)
+        st, qq = xe.planted_state(c.st, q, "wrap" if variant == "wrap"
+                                  else "mask4")
+        wrong = fm.law_f64([st], qq, xe.planted_mask(masks, variant, drop),
+                           target, values, False)
+        out = ((np.abs(wrong["joint"] - law["joint"])
+                > law["joint_band"]).any(1)
+               | (np.abs(wrong["base"] - law["base"]) > law["base_band"]))
+        print("  %s: %.0f %% of the rows leave the band" % (
+            variant, 100.0 * out.mean()))
+        assert out.any(), variant
+
+
+def test_wide_targets_cross_the_staging_tile():
+    """the staged kernels' launch geometry, restated
+    (eight_expect.staged_geometry): with NROWS query rows target 0 of the
+    eight-feature list stages 11 planes of 32 rows, 1408 bytes a group and
+    33 groups a tile -- two tiles at K = 43, three at K = 79; target 3
+    eight planes and 47 groups a tile -- two tiles at K = 79; the
+    ensemble's tile is taken from its largest K"""
+    def geometry(kinds, sh, target, K):
+        cand = fe.candidates_for(sh)
+        C = len(fe.default_candidates(sh) if cand is None else cand)
+        return xe.staged_geometry(kinds, target, C, K, NROWS)
+
+    c, swept = xe.case("eight"), xe.case("eight_swept")
+    kinds = [s.kind for s in c.osh]
+    assert (c.K, swept.K) == (43, 79)
+    g = geometry(kinds, c.osh[0], 0, c.K)
+    assert (g["planes"], g["rows"], g["tile"]) == (11, 32, 33)
+    assert xe.feature_lds(10, 0, 32) == 1408
+    assert g["lds"] <= xe.FEATURE_LDS_BUDGET
+    assert g["tiles"] >= 2
+    assert geometry(kinds, c.osh[0], 0, swept.K)["tiles"] >= 3
+    g = geometry(kinds, c.osh[3], 3, swept.K)
+    assert (g["planes"], g["tile"], g["tiles"]) == (8, 47, 2)
+    assert geometry(kinds, c.osh[7], 7, swept.K)["planes"] == 1
+    ens = xe.eight3()
+    ks = [m.K for m in ens.members]
+    g = geometry(kinds, c.osh[0], 0, max(ks))
+    assert g["tile"] == 33 and sorted(-(-k // g["tile"]) for k in ks) == [
+        1, 2, 2]

@@ -31,6 +31,7 @@ import numpy as np
 import pytest
 from scipy import stats
 
+import eight_expect as xe
 import oracle_lib as ol
 import predict_expect as pe
 import workloads
@@ -105,3 +106,38 @@ def test_draws_follow_the_float64_responsibilities():
     assert pvalue > 1e-4
     assert len(set(e["map"].tolist())) == 1
     assert e["map"][0] == p2g[int(np.argmax(p[0]))]
+
+
+# ---------------------------------------------------------------------------
+# five to eight features (tests/eight_expect.py)
+
+
+@pytest.mark.parametrize("name", xe.NAMES)
+def test_wide_oracle_logp_is_in_the_float64_band(name):
+    """every held-out row, none left out"""
+    c = xe.case(name)
+    e = c.expect()
+    assert e["scores"].shape == (c.nq, c.K)
+    assert np.all(np.isfinite(e["logp"]))
+    x = pe.excursion(e["logp"], c)
+    _, _, p = c.f64()
+    print("%s: F=%d, K=%d, %d held-out rows over %d drawn groups; worst "
+          "excursion / band %.3f; median largest responsibility %.2f" % (
+              name, len(c.osh), c.K, c.nq, len(set(e["draw"].tolist())),
+              x.max(), np.median(p.max(1))))
+    assert x.max() <= 1.0, name
+
+
+@pytest.mark.parametrize("variant", ["drop", "wrap"])
+@pytest.mark.parametrize("name", xe.NAMES)
+def test_wide_planted_variants_leave_the_band(name, variant):
+    """a law that leaves a feature >= 4 out, or reads feature f's words from
+    feature f & 3, is outside the band the oracle is inside"""
+    c = xe.case(name)
+    Lv, band, _ = c.f64()
+    st, q = xe.planted_state(c.st, c.qvals, variant)
+    wrong, _, _ = pe.logp_f64(st, q)
+    out = np.abs(wrong - Lv) > band
+    print("%s, %s: %.0f %% of the held-out rows leave the band" % (
+        name, variant, 100.0 * out.mean()))
+    assert out.any()

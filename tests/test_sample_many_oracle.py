@@ -28,9 +28,11 @@ import numpy as np
 import pytest
 from scipy import stats
 
+import eight_expect as xe
 import ensemble_expect as ee
 import feature_expect as fe
 import feature_many_expect as fm
+import marginals_expect as mx
 import oracle_lib as ol
 import sample_expect as sx
 import sample_many_expect as sm
@@ -325,3 +327,105 @@ def test_one_member_is_sample_rows_itself(config, le):
                         f, int(one["packed"][q])), seed, sm.DRAW_BASE + q, f)
                     if osh.kind in (ol.DD, ol.BB):
                         assert one["cols"][f][q] == w, (f, q)
+
+
+# ---------------------------------------------------------------------------
+# the eight-feature ensemble of tests/eight_expect.py
+
+_EIGHT3 = {}
+
+
+def eight3_draws():
+    """sample_many_expect.expect_many of eight3's 100 rows under random and
+    fixed masks, computed once"""
+    if not _EIGHT3:
+        ens = xe.eight3()
+        L = ol.oracle()
+        masks = xe.masks_for(ens.nq, 8, 41)
+        _EIGHT3["masks"] = masks
+        _EIGHT3["e"] = sm.expect_many(
+            [m.orc for m in ens.members], [m.gsh for m in ens.members],
+            ens.qvals, masks, L.orc_rng_seed(sm.DRAW_SEED),
+            L.orc_rng_seed(sm.MEMBER_SEED), sm.DRAW_BASE, False)
+    return _EIGHT3["e"], _EIGHT3["masks"]
+
+
+def base_law(states, qvals, masks):
+    """the float64 log of the mean over the members of the marginal density
+    of every row's observed cells, and its band: marginals_expect.law_f64
+    per distinct mask on the rows that carry it"""
+    pat = np.asarray(masks, np.int64) & 0xFF
+    Lv, band = np.zeros(len(pat)), np.zeros(len(pat))
+    for p in np.unique(pat):
+        idx = np.nonzero(pat == p)[0]
+        a, b = mx.law_f64(states, [np.asarray(v)[idx] for v in qvals],
+                          np.array([p], np.uint32), False)
+        Lv[idx], band[idx] = a[:, 0], b[:, 0]
+    return Lv, band
+
+
+def test_eight3_base_is_in_the_float64_band_and_the_variants_are_not():
+    """every row; then a law that never observes feature 7, one that takes
+    feature f's words from feature f & 3, one that reads the mask through
+    & 0xF"""
+    ens = xe.eight3()
+    e, masks = eight3_draws()
+    states = [m.st for m in ens.members]
+    assert np.all(np.isfinite(e["base"]))
+    assert len(set(e["member"].tolist())) == 3
+    Lv, band = base_law(states, ens.qvals, masks)
+    x = np.abs(e["base"] - Lv) / band
+    print("eight3: %d rows, worst excursion / band of base %.3f; members "
+          "drawn %s" % (ens.nq, x.max(), np.bincount(e["member"])))
+    assert x.max() <= 1.0
+    for variant in xe.VARIANTS:
+        qq = xe.planted_state(states[0], ens.qvals,
+                              "wrap" if variant == "wrap" else "mask4")[1]
+        wrong, _ = base_law(states, qq, xe.planted_mask(masks, variant, 7))
+        out = np.abs(wrong - Lv) > band
+        print("  %s: %.0f %% of the rows leave the band" % (
+            variant, 100.0 * out.mean()))
+        assert out.any(), variant
+
+
+def test_eight3_wb_and_member_are_predict_feature_manys():
+    """for the rows whose mask leaves the target unobserved"""
+    ens = xe.eight3()
+    e, masks = eight3_draws()
+    L = ol.oracle()
+
+    def bits(a):
+        return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+    for target in (0, 7):
+        rows = np.nonzero(((masks >> target) & 1) == 0)[0]
+        assert len(rows) >= 30
+        want = fm.expect_many(
+            [m.orc for m in ens.members], ens.qvals, masks, target, None,
+            L.orc_rng_seed(sm.DRAW_SEED), L.orc_rng_seed(sm.MEMBER_SEED),
+            sm.DRAW_BASE, False)
+        assert np.array_equal(bits(e["wb"][:, rows]),
+                              bits(want["wb"][:, rows]))
+        assert np.array_equal(bits(e["base"][rows]), bits(want["base"][rows]))
+        assert np.array_equal(e["member"][rows], want["member_draw"][rows])
+
+
+def test_eight3_cells_are_drawn_with_their_own_feature_as_the_key():
+    """every unobserved DD, BB and DPD cell is sample_expect.cell_word on the
+    drawn member's drawn group with key f, for f up to 7 (the other kinds
+    may part in a last place, see sample_expect)"""
+    ens = xe.eight3()
+    e, masks = eight3_draws()
+    seed = ol.oracle().orc_rng_seed(sm.DRAW_SEED)
+    cells = 0
+    for q in range(ens.nq):
+        m = ens.members[int(e["member"][q])]
+        for f, osh in enumerate(m.osh):
+            if (int(masks[q]) >> f) & 1 or osh.kind not in (ol.DD, ol.BB,
+                                                            ol.DPD):
+                continue
+            w = sx.cell_word(osh, m.orc.get_group(f, int(e["packed"][q])),
+                             seed, sm.DRAW_BASE + q, f)
+            assert e["cols"][f][q] == w, (q, f)
+            cells += 1
+    assert cells > 150
